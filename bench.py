@@ -9,12 +9,19 @@ profiles, bands) are built on the host and uploaded BEFORE the timed region; the
 result fetch (+ the all-gather of result slots for N > 1).  Divisions are dealt round-robin by size to the
 ranks; total work is fixed, so scaling is "strong".
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Prints ONE JSON line (rank 0).  `roofline.achieved` = in-band cells x 33 B (A = 2*Noll*8 + 1)
-/ forward-kernel time measured with HIP events on the stream the kernel runs on.  `cpu_baseline` = the
-reference's own alignC<recd_t> (oracle/_ref, kind "reference") or, when that is absent, the C restatement
-(oracle/, kind "port"), one host core, on a bounded sample of the same divisions."""
+/ forward-kernel time measured with HIP events on the stream the kernel runs on.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the read-outs that take runs
+of their own: `cpu_baseline` (the reference's own alignC<recd_t> (oracle/_ref, kind "reference") or, when that
+is absent, the C restatement (oracle/, kind "port"), on a bounded sample of the same divisions), the host
+builders, calcSpScore, g2g_align2_batch from host memory, the progressive-start sweep, the refinement loop
+against the reference's trajectory and the guide-tree stage.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's divisions) as DIR/<name>.npy, float64:
+division ids, DP scores, status words and the skeletons (concatenated corners + offsets per division)."""
 import argparse
 import json
 import os
@@ -255,6 +262,31 @@ def refinement_readout(ctx, args):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, divisions, out):
+    """The last timed step's results as float64 .npy files: per division its id, DP score and status word, and its skeleton
+    (skeleton_offsets[i]:skeleton_offsets[i+1] are division i's corners).  Beyond DUMP_LIMIT_BYTES a fixed every-k-th
+    sample of the divisions is written."""
+    import numpy as np
+    keep = list(range(len(out)))
+    size = lambda idx: 8 * (4 * len(idx) + 1 + 2 * sum(len(out[i][1]) for i in idx))
+    stride = 1
+    while size(keep) > DUMP_LIMIT_BYTES:
+        stride += 1
+        keep = list(range(0, len(out), stride))
+    skl = [np.asarray(out[i][1], np.float64).reshape(-1, 2) for i in keep]
+    arrays = {"division": np.array([divisions[i] for i in keep], np.float64),
+              "score": np.array([out[i][0] for i in keep], np.float64),
+              "status": np.array([out[i][2] for i in keep], np.float64),
+              "skeleton": np.concatenate(skl) if skl else np.zeros((0, 2), np.float64),
+              "skeleton_offsets": np.concatenate([[0], np.cumsum([len(x) for x in skl])]).astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -269,7 +301,13 @@ def main():
     ap.add_argument("--dna", action="store_true", help="non-default workload: DNA family, long-gap penalty (ls=3, Noll 3 kernels)")
     ap.add_argument("--shard-of", type=int, default=0,
                     help="rehearsal on ONE GPU: run only rank 0's share of an N-rank job (prints a line marked rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the read-outs beside the metric (CPU baselines, builders, calcSpScore, host-memory operator, "
+                         "progressive start, refinement, guide tree)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    extras = args.full and not args.no_cpu        # (--no-cpu = the timed region only: profiling runs)
 
     import numpy as np
     import torch
@@ -311,7 +349,7 @@ def main():
     # region; reported as config.builders (with the host builders timed beside them at N = 1).
     sw = sweep.Sweep(fam, alp, weighted=True, limit=args.limit or None, ctx=ctx)
     builders = {"groups_split_ms": 1e3 * sw.t_split, "device_batch_ms": 1e3 * sw.t_batch, "groups": 2 * len(sw)}
-    if world == 1 and not args.shard_of and not args.no_cpu:
+    if world == 1 and not args.shard_of and extras:
         t1 = time.perf_counter()
         sw_host = sweep.Sweep(fam, alp, weighted=True, limit=args.limit or None)
         builders["host_threads_ms_incl_split"] = 1e3 * (time.perf_counter() - t1)
@@ -389,24 +427,28 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mine, out)
+
     # f1 (not part of the metric): PreSpScore::calcSpScore of every new alignment on the resident batch
-    sp_ms = None
-    try:
-        if batch is None:
-            raise RuntimeError("sweep not resident")
-        sps = [op.spparams(p) for p in holders]
-        t1 = time.perf_counter()
-        fst = batch.spscore(sps, [skl for (_, skl, _) in out])
-        sp_ms = 1e3 * (time.perf_counter() - t1)
-        sp_bad = sum(1 for (_, _, st) in fst if st != 0)
-        gpu_sp = {int(k): float(v) for k, (v, _, st) in zip(mine, [x[:3] for x in fst]) if st == 0}
-    except Exception as e:                                   # never let the extra row break the benchmark line
-        sp_ms, sp_bad = None, str(e)
-        gpu_sp = None
+    sp_ms, gpu_sp = None, None
+    if args.full:
+        try:
+            if batch is None:
+                raise RuntimeError("sweep not resident")
+            sps = [op.spparams(p) for p in holders]
+            t1 = time.perf_counter()
+            fst = batch.spscore(sps, [skl for (_, skl, _) in out])
+            sp_ms = 1e3 * (time.perf_counter() - t1)
+            sp_bad = sum(1 for (_, _, st) in fst if st != 0)
+            gpu_sp = {int(k): float(v) for k, (v, _, st) in zip(mine, [x[:3] for x in fst]) if st == 0}
+        except Exception as e:                               # never let the extra row break the benchmark line
+            sp_ms, sp_bad = None, str(e)
+            gpu_sp = None
     # (not part of the metric either) the whole operator from host memory: g2g_align2_batch = pack + upload + kernels +
     # fetch + stdskl + end check, i.e. what a caller pays per sweep when nothing is resident
     e2e_ms = None
-    if world == 1 and not args.shard_of and not args.no_cpu:     # (--no-cpu = the timed region only: profiling runs)
+    if world == 1 and not args.shard_of and extras:
         try:
             e2e_ms = float("inf")
             for _ in range(2):                             # (the first call also allocates its device arena: steady state = min)
@@ -422,7 +464,7 @@ def main():
     prog = None
     ppath = os.path.join(ROOT, "tests", "golden", "msa", "prog256x1024.npz")
     if world == 1 and not args.shard_of and not args.dna and not args.limit and args.nseq == 256 and args.length == 1024 and args.seed == 1 \
-            and os.path.exists(ppath) and not args.no_cpu:
+            and os.path.exists(ppath) and extras:
         try:
             sw2 = sweep.Sweep(fam, alp, weighted=True, codes=np.load(ppath)["codes"])
             b2 = ctx.prepare([_H(p.problem) for p in sw2.pwds])
@@ -444,7 +486,7 @@ def main():
     #    byte for byte (then the SP-score delta of the refined alignment vs the reference is exactly 0)
     #  - the guide-tree stage (f3: alnScoreD for all pairs of the bench family, one launch)
     refinement = guide_tree = None
-    if world == 1 and not args.shard_of and not args.limit and not args.no_cpu:
+    if world == 1 and not args.shard_of and not args.limit and extras:
         try:
             refinement = refinement_readout(ctx, args)
         except Exception as e:
@@ -536,7 +578,7 @@ def main():
         if args.shard_of > 1 and world == 1:
             line["rehearsal"] = "rank 0's share of a %d-rank job on one GPU: %d divisions, %.4g cells, %.1f ms per step" % (
                 args.shard_of, len(mine), my_cells, ms_per_step)
-        if not args.no_cpu and world == 1:                # (rank 0 at N = 1 only)
+        if extras and world == 1:                         # (rank 0 at N = 1 only)
             one = cpu_baseline(sw, args.cpu_seconds, {int(k): float(o[0]) for k, o in zip(mine, out)}, gpu_sp)
             allc = None
             try:

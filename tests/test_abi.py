@@ -54,8 +54,11 @@ def test_stdskl_host_matches_reference(built):
 
 def test_no_device_fails_loudly(built):
     """Without a GPU the product must refuse, never compute on the host."""
-    import torch
-    if torch.cuda.is_available():
+    import subprocess, sys
+    # torch asked in a child process: its own HIP runtime, initialised here beside the one libg2g.so already loaded, would
+    # leave the library without a device for the rest of the session
+    p = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True)
+    if p.returncode == 0 and p.stdout.split()[-1:] == ["True"]:
         pytest.skip("GPU present")
     from prrn_aln_amd import engine
     from prrn_aln_amd._lib import G2GError

@@ -4,6 +4,7 @@ claim is tests/test_gpu_dropin.py.)  Skips when oracle/_ref was not built (no /r
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -17,11 +18,10 @@ pytestmark = pytest.mark.skipif(not all(os.path.exists(p) for p in BIN.values())
 
 
 def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
+    # asked in a child process: torch's own HIP runtime, initialised here beside the one libg2g.so already loaded, would leave
+    # the library without a device for the rest of the session
+    p = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True)
+    return p.returncode == 0 and p.stdout.split()[-1:] == ["True"]
 
 
 def _run(exe, args, cwd, **env):

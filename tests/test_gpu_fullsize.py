@@ -129,10 +129,12 @@ def test_dna_ls3_resident_sweep_properties_and_sampled_parity(ctx):
         def __init__(self, q): self.c = q
     hs = [H(pw.problem) for pw in sw.pwds]
     b = ctx.prepare(hs)                                   # inputs of all 317 divisions resident
-    b.run(); r1 = b.fetch()
-    b.run(); r2 = b.fetch()
-    assert b.recovery() == (0, 0, 0)
-    b.free()
+    try:                                                  # (freed before the module's context closes, whatever happens)
+        b.run(); r1 = b.fetch()
+        b.run(); r2 = b.fetch()
+        assert b.recovery() == (0, 0, 0)
+    finally:
+        b.free()
     from prrn_aln_amd import engine as eng
     for pw, (scr, cells, tr, st), (scr2, _, tr2, st2) in zip(sw.pwds, r1, r2):
         q = pw.problem

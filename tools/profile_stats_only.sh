@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export G2G_WARN=1
 [ -n "$DEBUGLOG" ] && export G2G_DEBUG=1
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- python3 $R/bench.py --steps ${2:-4} --warmup 1 --no-cpu > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- python3 $R/bench.py --steps ${2:-4} --warmup 1 --full --no-cpu > $O/bench.json 2> $O/bench.err || exit 1
 cp $O/stats/s_kernel_stats.csv $O/kernel_stats.csv
 grep -c "timed out" $O/bench.err
 grep "timed out" $O/bench.err | head -5

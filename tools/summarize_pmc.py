@@ -20,7 +20,7 @@ hbm = sum((per[k].get("FETCH_SIZE", 0) + per[k].get("WRITE_SIZE", 0)) * 1024 for
 out = {"per_kernel": {k: dict(v) for k, v in per.items()},
        "units": "FETCH_SIZE / WRITE_SIZE in KiB (rocprofv3 derived counters, summed over XCDs; one sweep = bench.py "
                 "--steps 1 --warmup 0); SQ_WAVE_CYCLES / SQ_ACTIVE_* / SQ_WAIT_* in quad-cycles",
-       "command": "tools/profile_round.sh: rocprofv3 --pmc <set> -- python3 bench.py --steps 1 --warmup 0 --no-cpu, one set per pass",
+       "command": "tools/profile_round.sh: rocprofv3 --pmc <set> -- python3 bench.py --steps 1 --warmup 0 --full --no-cpu, one set per pass",
        "hbm_bytes_forward_kernels": hbm}
 json.dump(out, open(os.path.join(O, "pmc.json"), "w"), indent=1)
 fetch = sum(per[k].get("FETCH_SIZE", 0) * 1024 for k in fwd)
