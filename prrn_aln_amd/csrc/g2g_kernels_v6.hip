@@ -109,13 +109,17 @@ __device__ __forceinline__ DH<NE> dh_load6(const lu32 *p, const LS6 &W, const in
 }
 // (a terminator's glen = -1 is looked up as 0: its result is never used)
 __device__ __forceinline__ unsigned v6_key(const int g) { return ((unsigned) (g < 0 ? 0 : g) << 16) | 0xFFFFu; }
-// the entry that governs static gap length g (GapLenSD, gfreq.h:67): the largest entry <= key
+// the entry that governs static gap length g (GapLenSD, gfreq.h:67): the largest entry <= key (entry 0 when none is).
+// The head is non-decreasing, so that entry is key - min_k (key - e[k]) in wrapping u32 arithmetic: an entry above the key
+// wraps to 2^32 - (e[k] - key), above the distance key - e[j] of every entry at or below it.  Independent subtractions and
+// a min tree instead of a compare / select chain on one VCC (each link of which waited two wait states for its select).
 template <int NE, bool SCAN>
 __device__ __forceinline__ unsigned dh_ent(const unsigned key, const DH<NE> &h, const LS6 &W, const int I)
 {
-    unsigned e = h.e[0];
+    unsigned t = key - h.e[0];
     V6_UNROLL
-    for (int k = 1; k < NE; ++k) e = key >= h.e[k] ? h.e[k] : e;
+    for (int k = 1; k < NE; ++k) t = __builtin_elementwise_min(t, key - h.e[k]);
+    unsigned e = key >= h.e[0] ? key - t : h.e[0];
     if (SCAN) {
         const bool more = key >= h.x;
         if (__ballot(more)) {                               // more than NE entries at or below g
@@ -277,7 +281,10 @@ __device__ __forceinline__ double v6_xmerge(const DH<NE> &ha, const DH<NE> &hb, 
     for (int kk = lmax - 1; kk >= 0; --kk) {
         const bool valid = kk < B.lens;
         const SE6 e = se6_read(B.rs, B.os + (valid ? kk : 0));
-        const unsigned i = valid ? dh_stretch<NE, SCAN>(e.key, hb, W, W.ib) : 0u;
+        // (looked up in every lane -- the ring entry at the list's start where kk is beyond the list -- and masked by a select: guarded,
+        // the chain sat in an exec-mask branch of its own)
+        const unsigned iv = dh_stretch<NE, SCAN>(e.key, hb, W, W.ib);
+        const unsigned i = valid ? iv : 0u;
         if (RV) Sh = i >= jh ? e.f : Sh;
         V6_UNROLL
         for (int d = 0; d < N; ++d)
