@@ -23,6 +23,7 @@
 #include "g2g_internal.h"
 
 #include "g2g_kernels.hip"          // one translation unit: kernels + launcher (no -fgpu-rdc needed)
+#include "g2g_strip.h"            // primitives and scaffold of the strip kernels below
 #include "g2g_kernels_v2.hip"
 #include "g2g_kernels_v3.hip"
 #include "g2g_kernels_v6.hip"

@@ -23,23 +23,6 @@
 // fence only.
 #include <hip/hip_runtime.h>
 
-struct RS { double val; int dir, glb; };                  // record scalars
-__device__ __forceinline__ RS rs_black() { RS r; r.val = NEVSEL; r.dir = 0; r.glb = 0; return r; }
-// lane t <- lane t-1 over the whole wave: one DPP move per dword (wave_shr:1), no LDS crossbar round trip
-__device__ __forceinline__ int dpp_up1(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ RS rs_up(const RS &x)
-{
-    RS r;
-    r.val = __hiloint2double(dpp_up1(__double2hiint(x.val)), dpp_up1(__double2loint(x.val)));
-    r.dir = dpp_up1(x.dir); r.glb = dpp_up1(x.glb);
-    return r;
-}
-__device__ __forceinline__ RS rs_sel(bool c, const RS &x, const RS &y)
-{
-    RS r; r.val = c ? x.val : y.val; r.dir = c ? x.dir : y.dir; r.glb = c ? x.glb : y.glb; return r;
-}
-
-
 // byte offsets of the LDS regions of a v3 launch (host: v3_lds_plan)
 struct V3Lds { int rows, black, stsc, aglen, afreq, boff, bglen, bfreq, svals, sink, total; };
 
@@ -523,6 +506,11 @@ __device__ __forceinline__ void v3_rec_store(unsigned *dst, int capa, int capb, 
     for (int k = 0; k < capb; ++k) dst[4 + capa + k] = lb[k];
 }
 
+struct V3Strip : StripTraits {
+    static constexpr bool PUB_COL = true;
+    static __device__ __forceinline__ void acquire() { G2G_ACQUIRE(); }
+    static __device__ __forceinline__ void release() { G2G_RELEASE(); }
+};
 template <int KIND, bool NOLL3, int NA>
 __device__ __forceinline__ void v3_tile(const DevProb &Pmem, lchar *lds, const V3Lds LO, const int ti, const int tj, const int nsteps, const int C,
                         const int *prog_up = 0, int *prog_self = 0, int *dbg = 0, const int pgen = 0, const int pint = 32,
@@ -677,32 +665,11 @@ __device__ __forceinline__ void v3_tile(const DevProb &Pmem, lchar *lds, const V
             if (wantG) { stage_put(SLOT_G(col), 3 + (col & 1), rg); if (NOLL3) stage_put(SLOT_G2(col), 5 + (col & 1), rg2); }
         }
     };
-    int avail = prog_up ? 0 : 0x7fffffff;                    // corner columns of the strip above known to be final
-    const int penc = (pgen & 0x7FF) << 20;
-    auto need = [&](const int col) {                       // wave-uniform: every lane polls, nobody branches alone
-        const int want = penc | (col < 0xFFFFF ? col : 0xFFFFF);
-        if (prog_up && want > avail) {
-            avail = g2g_wait_ge(prog_up, want, dbg, failp, ti);
-            G2G_ACQUIRE();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    };
-    auto publish = [&](const int col) {                    // corners <= col of this strip's last row are in HBM
-        if (prog_self) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            G2G_RELEASE();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(prog_self + G2G_DIAG + 8, col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (as the v2 strips: the wave's last publish, for the time-out report)
-            G2G_POST(prog_self, penc | (col < 0 ? 0 : col < 0xFFFFF ? col : 0xFFFFF));
-        }
-    };
+    StripSync S = strip_sync(prog_up, prog_self, dbg, failp, pgen, ti);
     if (lane < 28) stsc[lane] = 0;
     team_sync();
-    need(cbase + 1 <= c1 ? cbase + 1 : cbase);
-    if (prog_self) {                                       // where this strip runs: for the time-out report of whoever waits for it (g2g_wait_ge)
-        __hip_atomic_store(prog_self + G2G_DIAG + 3, (int) __builtin_amdgcn_s_getreg((31 << 11) | 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(prog_self + G2G_DIAG + 4, 0x100 | ((int) __builtin_amdgcn_s_getreg((31 << 11) | 20) & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    strip_need<V3Strip>(S, cbase + 1 <= c1 ? cbase + 1 : cbase);
+    strip_where(S);
     {
         unsigned rh = 0, rg = 0, rg2 = 0;
         stage_load(cbase, false, rh, rg, rg2);
@@ -773,7 +740,7 @@ __device__ __forceinline__ void v3_tile(const DevProb &Pmem, lchar *lds, const V
         if (wr_rows && s > 0) flush_rows(n0 - 1 - llast);
         G2G_HB_STEP(prog_self, 0, s)                       // (places, v3: 1 top of the step, 5 behind publish / score block, 6 loads issued, 7 cell done)
         G2G_HB(prog_self, 0, 1)
-        if (prog_self && s > 0 && (s & (pint - 1)) == 0) publish(n0 - llast);
+        if (prog_self && s > 0 && (s & (pint - 1)) == 0) strip_publish<V3Strip>(S, n0 - llast);
         if (own_sim && !sim_direct && (s & 63) == 0) { simblk_fill(P, SB, (s >> 6) + 1, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         G2G_HB(prog_self, 0, 5)
         // -- hand-over from the row above: what lane t-1 produced one step ago is my upper neighbour, what it
@@ -781,22 +748,7 @@ __device__ __forceinline__ void v3_tile(const DevProb &Pmem, lchar *lds, const V
         hd = hu;
         hu = rs_up(oH); gu = rs_up(oG);
         if (NOLL3) g2u = rs_up(oG2);
-        {
-            const lu32 *q = stsc + SLOT_H(n0) * 4;
-            RS t; t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-            hd = rs_sel(lane == 0, t, hd);
-            q = stsc + SLOT_H(n0 + 1) * 4;
-            t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-            hu = rs_sel(lane == 0, t, hu);
-            q = stsc + (3 + ((n0 + 1) & 1)) * 4;
-            t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-            gu = rs_sel(lane == 0, t, gu);
-            if (NOLL3) {
-                q = stsc + (5 + ((n0 + 1) & 1)) * 4;
-                t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-                g2u = rs_sel(lane == 0, t, g2u);
-            }
-        }
+        strip_handover<V3Strip, NOLL3>(stsc, n0, lane, hd, hu, gu, g2u);
         // -- loads for the next step: next column's score/thickness; the strip above's records two columns ahead
         double sim_nx = 0, bc_nx = 0;
         if (active) {
@@ -804,7 +756,7 @@ __device__ __forceinline__ void v3_tile(const DevProb &Pmem, lchar *lds, const V
             if (n + 1 < hi) { sim_nx = sim_direct ? sim_arow[sim_bres[n + 1]] : own_sim ? (double) *simblk_at(SB, lane, n + 1) : simrow[n + 1]; bc_nx = thk_at(b, n + 1)[0]; }
         }
         st_prev = n0 + 1 < hi0 && n0 + 2 <= c1;
-        if (st_prev) { need(n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
+        if (st_prev) { strip_need<V3Strip>(S, n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
         RS myH = oH, myG = oG, myG2 = oG2;                 // (the produced records of this step)
         if (active) {
             const bool do_hori = n > b.left;
@@ -861,21 +813,19 @@ __device__ __forceinline__ void v3_tile(const DevProb &Pmem, lchar *lds, const V
     }
     if (p_act) P.trace[p_tri] = (uint8_t) p_trb;
     if (wr_rows) flush_rows(cbase + nsteps - 1 - llast);
-    publish(0xFFFFF);
+    strip_publish<V3Strip>(S, 0xFFFFF);
 #undef V3_L
 }
 
+#define V3_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
+NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, V3Lds LO, int C, int sweep, int pro_off, double *simscr)
 #define V3_KERNEL(NAME, KIND, N3, NA, WPE)                                                           \
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))      \
-NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, V3Lds LO, int C, int sweep, int pro_off, double *simscr) \
+V3_SIG(NAME, __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))))                   \
 {                                                                                                   \
     extern __shared__ __attribute__((aligned(16))) char g2g_lds[];                                  \
     li32 *s_vals = (li32 *) ((lchar *) g2g_lds + LO.svals);                                         \
     for (;;) {                                                                                      \
-        s_vals[threadIdx.x] = atomicAdd(qhead, threadIdx.x == 0 ? 1 : 0);                           \
-        __syncthreads();                                                                            \
-        const int t = __builtin_amdgcn_readfirstlane(s_vals[0]);                                    \
-        __syncthreads();                                                                            \
+        const int t = strip_pop(qhead, s_vals);                                                     \
         if (t >= ntiles) break;                                                                     \
         const V2Tile T = tiles[t];                                                                  \
         if (T.ti < 0) {           /* a boundary chain (v2_chain_tile, g2g_kernels_v2.hip) */         \
@@ -884,15 +834,7 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
             continue;                                                                               \
         }                                                                                           \
         int *failp = done + done[G2G_HDR + 2] + T.prob;                                                      \
-        if (threadIdx.x == 0) s_vals[0] = g2g_dp_failed(failp) ? 1 : 0;      /* (one reader: the branch must be uniform) */ \
-        __syncthreads();                                                                            \
-        const int dp_dead = s_vals[0];                                                              \
-        __syncthreads();                                                                            \
-        if (dp_dead) {                    /* this DP lost a wait: its strips are skipped, dependents released */ \
-            if (threadIdx.x == 0) G2G_POST(done + T.self, sweep ? (((gen & 0x7FF) << 20) | 0xFFFFF) : gen); \
-            __syncthreads();                                                                        \
-            continue;                                                                               \
-        }                                                                                           \
+        if (strip_dp_dead(failp, s_vals)) { strip_release(done + T.self, sweep ? strip_done_word(gen) : gen); continue; } \
         const int *pl = (sweep && T.dep_left >= 0) ? done + T.dep_left : (const int *) 0;            \
         /* sweep: strips as a pipeline on progress counters; else tiles on completion flags.  ONE call site of the   \
            tile function, or it is not inlined and its frame lands in scratch memory */                             \
@@ -930,6 +872,5 @@ V3_KERNEL(g2g_v3_hf3, 1, true, 0, 2)
 V3_KERNEL(g2g_v3r_hf2, 1, false, G2G_V3_NA, G2G_V3R_WPE)
 V3_KERNEL(g2g_v3r_hf3, 1, true, G2G_V3_NA, 1)
 #else
-#define V3_KERNEL_DECL(NAME) extern "C" __global__ void NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, V3Lds LO, int C, int sweep, int pro_off, double *simscr);
-V3_KERNEL_DECL(g2g_v3_hf2) V3_KERNEL_DECL(g2g_v3_hf3) V3_KERNEL_DECL(g2g_v3r_hf2) V3_KERNEL_DECL(g2g_v3r_hf3)
+V3_SIG(g2g_v3_hf2, ); V3_SIG(g2g_v3_hf3, ); V3_SIG(g2g_v3r_hf2, ); V3_SIG(g2g_v3r_hf3, );
 #endif

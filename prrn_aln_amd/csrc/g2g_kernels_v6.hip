@@ -30,12 +30,6 @@
 // register copy of the whole descriptor into scratch memory (1.1 KB per lane): the kernel has no private segment now.
 #include <hip/hip_runtime.h>
 
-// HBM pointers of the sweep carry their address space: a generic pointer compiles to flat_load/flat_store, which also
-// occupy the LDS counter (every wait for an LDS read would then wait for the global loads in flight as well)
-#define GLB __attribute__((address_space(1)))
-template <class T> __device__ __forceinline__ const GLB T *glb(const T *p) { return (const GLB T *) p; }
-template <class T> __device__ __forceinline__ GLB T *glbw(T *p) { return (GLB T *) p; }
-
 // -DG2G_V6_STAMP: cycle shares of the phases of a step (diagnostics; s_memtime deltas summed per strip, then atomically)
 #ifdef G2G_V6_STAMP
 __device__ unsigned long long g2g_v6_stamp_acc[16];
@@ -477,6 +471,21 @@ __device__ __forceinline__ bool v6_cell_pf(const DevProb &P, const LS6 &W, const
 #define V6_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
 #define V6_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent")
 #endif
+// diagnostic heartbeat (build with -DG2G_V6_HEARTBEAT): step counter and a marker of the place in the step, stored next to the
+// strip's progress word; the report of a time-out reads them (g2g_wait_ge).  Off by default: ten 4-byte write-through stores
+// per step are ~30 GB/s of fabric traffic for nothing.
+#if defined(G2G_V6_HEARTBEAT) || defined(G2G_HEARTBEAT)
+#define V6_MARK(k) { if (prog_self) __hip_atomic_store(prog_self + G2G_DIAG + 2, (k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#define V6_BEAT(s) { if (prog_self) __hip_atomic_store(prog_self + G2G_DIAG + 1, (s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#else
+#define V6_MARK(k)
+#define V6_BEAT(s)
+#endif
+struct V6Strip : StripTraits {
+    static __device__ __forceinline__ void acquire() { V6_ACQUIRE(); }
+    static __device__ __forceinline__ void release() { V6_RELEASE(); }
+    static __device__ __forceinline__ void mark(int *prog_self, int k) { V6_MARK(k) }
+};
 template <bool NOLL3, int NA>
 __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const V6Lds LO, const int ti, const int nsteps,
                                          const int *prog_up, int *prog_self, int *dbg, const int pgen, const int pint, const int *prog_left,
@@ -637,42 +646,11 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
             if (wantG) { stage_put(SLOT_G(col), 3 + (col & 1), rg); if (NOLL3) stage_put(SLOT_G2(col), 5 + (col & 1), rg2); }
         }
     };
-    int avail = prog_up ? 0 : 0x7fffffff;                  // corner columns of the strip above known to be final
-    const int penc = (pgen & 0x7FF) << 20;
-    auto need = [&](const int col) {                       // wave-uniform: every lane polls, nobody branches alone
-        const int want = penc | (col < 0xFFFFF ? col : 0xFFFFF);
-        if (prog_up && want > avail) {
-            avail = g2g_wait_ge(prog_up, want, dbg, failp, ti);
-            V6_ACQUIRE();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    };
-// diagnostic heartbeat (build with -DG2G_V6_HEARTBEAT): step counter and a marker of the place in the step, stored next to the
-// strip's progress word; the report of a time-out reads them (g2g_wait_ge).  Off by default: ten 4-byte write-through stores
-// per step are ~30 GB/s of fabric traffic for nothing.
-#if defined(G2G_V6_HEARTBEAT) || defined(G2G_HEARTBEAT)
-#define V6_MARK(k) { if (prog_self) __hip_atomic_store(prog_self + G2G_DIAG + 2, (k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#define V6_BEAT(s) { if (prog_self) __hip_atomic_store(prog_self + G2G_DIAG + 1, (s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#else
-#define V6_MARK(k)
-#define V6_BEAT(s)
-#endif
-    auto publish = [&](const int col) {                    // corners <= col of this strip's last row are in HBM
-        if (prog_self) {
-            V6_MARK(9)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            V6_MARK(10)
-            V6_RELEASE();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            V6_MARK(11)
-            G2G_POST(prog_self, penc | (col < 0 ? 0 : col < 0xFFFFF ? col : 0xFFFFF));
-            V6_MARK(12)
-        }
-    };
+    StripSync S = strip_sync(prog_up, prog_self, dbg, failp, pgen, ti);
     if (lane < 28) stsc[lane] = 0;
     team_sync();
     refill(cbase + V6_AHEAD);
-    need(cbase + 1 <= c1 ? cbase + 1 : cbase);
+    strip_need<V6Strip>(S, cbase + 1 <= c1 ? cbase + 1 : cbase);
     {
         unsigned rh = 0, rg = 0, rg2 = 0;
         stage_load(cbase, false, rh, rg, rg2);
@@ -685,7 +663,7 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
     // per-row constants and one-step-ahead register pipelines (column score, b's column thickness, list offsets)
     const double a_efq = row_ok ? thk_at(a, m)[2] : 0;
     const double pua_row = row_ok ? unpa(P, m, nlo) : 0;                 // fwd2c.h:380 (402 when a.inex.nils)
-    SimBlk SB; SB.buf = (GLBV3 double *) simscr; SB.cbase = cbase;      // strip-local column scores (g2g_kernels_v3.hip)
+    SimBlk SB; SB.buf = (GLBV3 double *) simscr; SB.cbase = cbase;      // strip-local column scores (g2g_strip.h)
     simblk_fill(P, SB, 0, m0, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     double sim_cur = 0, bc_cur = 0;
@@ -730,10 +708,7 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
     unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long st_t = __builtin_amdgcn_s_memtime();
 #endif
-    if (prog_self) {                                       // where this strip runs (read by the report of a time-out, g2g_wait_ge)
-        __hip_atomic_store(prog_self + G2G_DIAG + 3, (int) __builtin_amdgcn_s_getreg((31 << 11) | 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(prog_self + G2G_DIAG + 4, 0x100 | ((int) __builtin_amdgcn_s_getreg((31 << 11) | 20) & 15), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    strip_where(S);
     for (int s = 0; s < nsteps; ++s) {
         V6_STAMP(9)
         V6_BEAT(s)
@@ -745,29 +720,14 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
         if (st_prev) stage_store(n0 + 1, vert0, st_h, st_g, st_g2);
         if (p_act) trace[p_tri] = (uint8_t) p_trb;
         if (wr_rows && s > 0) flush_rows(n0 - 1 - llast);
-        if (prog_self && s > 0 && (s & (pint - 1)) == 0) publish(n0 - llast);
+        if (prog_self && s > 0 && (s & (pint - 1)) == 0) strip_publish<V6Strip>(S, n0 - llast);
         if ((s & (V6_FEED - 1)) == 0) { V6_MARK(2) refill(n0 + V6_AHEAD); team_sync(); }
         if ((s & 63) == 0) { V6_MARK(3) simblk_fill(P, SB, (s >> 6) + 1, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         // -- hand-over from the row above
         hd = hu;
         hu = rs_up(oH); gu = rs_up(oG);
         if (NOLL3) g2u = rs_up(oG2);
-        {
-            const lu32 *q = stsc + SLOT_H(n0) * 4;
-            RS t; t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-            hd = rs_sel(lane == 0, t, hd);
-            q = stsc + SLOT_H(n0 + 1) * 4;
-            t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-            hu = rs_sel(lane == 0, t, hu);
-            q = stsc + (3 + ((n0 + 1) & 1)) * 4;
-            t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-            gu = rs_sel(lane == 0, t, gu);
-            if (NOLL3) {
-                q = stsc + (5 + ((n0 + 1) & 1)) * 4;
-                t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = (int) q[3];
-                g2u = rs_sel(lane == 0, t, g2u);
-            }
-        }
+        strip_handover<V6Strip, NOLL3>(stsc, n0, lane, hd, hu, gu, g2u);
         // -- loads for the next step: next column's score / thickness / list offsets; the strip above's records two columns ahead
         double sim_nx = 0, bc_nx = 0;
         int os_nx = 0, oe_nx = 0, ot_nx = 0, te_nx = 0;
@@ -782,7 +742,7 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
             }
         }
         st_prev = n0 + 1 < hi0 && n0 + 2 <= c1;
-        if (st_prev) { V6_MARK(4) need(n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
+        if (st_prev) { V6_MARK(4) strip_need<V6Strip>(S, n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
         V6_MARK(5)
         RS myH = oH, myG = oG, myG2 = oG2;                 // (the produced records of this step)
         V6_STAMP(0)
@@ -842,22 +802,20 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
 #endif
     if (p_act) trace[p_tri] = (uint8_t) p_trb;
     if (wr_rows) flush_rows(cbase + nsteps - 1 - llast);
-    publish(0xFFFFF);
+    strip_publish<V6Strip>(S, 0xFFFFF);
     V6_MARK(8)
 #undef V6_L
 }
 
+#define V6_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
+NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, V6Lds LO, int pint, int pro_off, double *simscr, unsigned *twin, int twin_dw)
 #define V6_KERNEL(NAME, N3, NA, WPE)                                                                 \
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))      \
-NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, V6Lds LO, int pint, int pro_off, double *simscr, unsigned *twin, int twin_dw) \
+V6_SIG(NAME, __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))))                   \
 {                                                                                                   \
     extern __shared__ __attribute__((aligned(16))) char g2g_lds[];                                  \
     li32 *s_vals = (li32 *) ((lchar *) g2g_lds + LO.svals);                                         \
     for (;;) {                                                                                      \
-        s_vals[threadIdx.x] = atomicAdd(qhead, threadIdx.x == 0 ? 1 : 0);                           \
-        __syncthreads();                                                                            \
-        const int t = __builtin_amdgcn_readfirstlane(s_vals[0]);                                    \
-        __syncthreads();                                                                            \
+        const int t = strip_pop(qhead, s_vals);                                                     \
         if (t >= ntiles) break;                                                                     \
         const V2Tile T = tiles[t];                                                                  \
         if (T.ti < 0) {           /* a boundary chain (v2_chain_tile, g2g_kernels_v2.hip) */         \
@@ -866,15 +824,7 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
             continue;                                                                               \
         }                                                                                           \
         int *failp = done + done[G2G_HDR + 2] + T.prob;                                                      \
-        if (threadIdx.x == 0) s_vals[0] = g2g_dp_failed(failp) ? 1 : 0;      /* (one reader: the branch must be uniform) */ \
-        __syncthreads();                                                                            \
-        const int dp_dead = s_vals[0];                                                              \
-        __syncthreads();                                                                            \
-        if (dp_dead) {                    /* this DP lost a wait: its strips are skipped, dependents released */ \
-            if (threadIdx.x == 0) G2G_POST(done + T.self, ((gen & 0x7FF) << 20) | 0xFFFFF); \
-            __syncthreads();                                                                        \
-            continue;                                                                               \
-        }                                                                                           \
+        if (strip_dp_dead(failp, s_vals)) { strip_release(done + T.self, strip_done_word(gen)); continue; } \
         const int *pl = T.dep_left >= 0 ? done + T.dep_left : (const int *) 0;                      \
         const int *pu = T.dep_up >= 0 ? done + T.dep_up : (const int *) 0;                          \
         __syncthreads();                                                                            \
@@ -894,6 +844,5 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
 V6_KERNEL(g2g_v6_pf2, false, G2G_V6_NA, 1)
 V6_KERNEL(g2g_v6_pf3, true, G2G_V6_NA3, 1)
 #else
-#define V6_KERNEL_DECL(NAME) extern "C" __global__ void NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, V6Lds LO, int pint, int pro_off, double *simscr, unsigned *twin, int twin_dw);
-V6_KERNEL_DECL(g2g_v6_pf2) V6_KERNEL_DECL(g2g_v6_pf3)
+V6_SIG(g2g_v6_pf2, ); V6_SIG(g2g_v6_pf3, );
 #endif

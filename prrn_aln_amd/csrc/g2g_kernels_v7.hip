@@ -56,6 +56,7 @@ __device__ __forceinline__ void v7_chain_tile(const DevProb &Pmem, const int whi
     chain_publish(prog, penc, 0xFFFFF);
 }
 
+struct V7Strip : StripTraits { static constexpr bool REC_GLB = false; };      // (and no strip_where: no HW_ID for the stall report)
 template <bool NOLL3>
 __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const int ti, const int nsteps,
                                          const int *prog_up, int *prog_self, int *dbg, const int pgen, const int pint, const int *prog_left,
@@ -115,27 +116,10 @@ __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const 
             if (wantG) { stsc[(3 + (col & 1)) * 4 + lane] = rg; if (NOLL3) stsc[(5 + (col & 1)) * 4 + lane] = rg2; }
         }
     };
-    int avail = prog_up ? 0 : 0x7fffffff;
-    const int penc = (pgen & 0x7FF) << 20;
-    auto need = [&](const int col) {                       // wave-uniform: every lane polls, nobody branches alone
-        const int want = penc | (col < 0xFFFFF ? col : 0xFFFFF);
-        if (prog_up && want > avail) {
-            avail = g2g_wait_ge(prog_up, want, dbg, failp, ti);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    };
-    auto publish = [&](const int col) {
-        if (prog_self) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            G2G_POST(prog_self, penc | (col < 0 ? 0 : col < 0xFFFFF ? col : 0xFFFFF));
-        }
-    };
+    StripSync S = strip_sync(prog_up, prog_self, dbg, failp, pgen, ti);
     if (lane < 28) stsc[lane] = 0;
     team_sync();
-    need(cbase + 1 <= c1 ? cbase + 1 : cbase);
+    strip_need<V7Strip>(S, cbase + 1 <= c1 ? cbase + 1 : cbase);
     {
         unsigned rh = 0, rg = 0, rg2 = 0;
         stage_load(cbase, false, rh, rg, rg2);
@@ -184,34 +168,19 @@ __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const 
         if (st_prev) stage_store(n0 + 1, vert0, st_h, st_g, st_g2);
         if (p_act) trace[p_tri] = (uint8_t) p_trb;
         if (wr_rows && s > 0) flush_rows(n0 - 1 - llast);
-        if (prog_self && s > 0 && (s & (pint - 1)) == 0) publish(n0 - llast);
+        if (prog_self && s > 0 && (s & (pint - 1)) == 0) strip_publish<V7Strip>(S, n0 - llast);
         if ((s & 63) == 0) { simblk_fill(P, SB, (s >> 6) + 1, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         hd = hu;
         hu = rs_up(oH); gu = rs_up(oG);
         if (NOLL3) g2u = rs_up(oG2);
-        {
-            const lu32 *q = stsc + SLOT_H(n0) * 4;
-            RS t; t.val = *(const lf64 *) q; t.dir = (int) q[2]; t.glb = 0;
-            hd = rs_sel(lane == 0, t, hd);
-            q = stsc + SLOT_H(n0 + 1) * 4;
-            t.val = *(const lf64 *) q; t.dir = (int) q[2];
-            hu = rs_sel(lane == 0, t, hu);
-            q = stsc + (3 + ((n0 + 1) & 1)) * 4;
-            t.val = *(const lf64 *) q; t.dir = (int) q[2];
-            gu = rs_sel(lane == 0, t, gu);
-            if (NOLL3) {
-                q = stsc + (5 + ((n0 + 1) & 1)) * 4;
-                t.val = *(const lf64 *) q; t.dir = (int) q[2];
-                g2u = rs_sel(lane == 0, t, g2u);
-            }
-        }
+        strip_handover<V7Strip, NOLL3>(stsc, n0, lane, hd, hu, gu, g2u);
         double sim_nx = 0, bc_nx = 0, be_nx = 0;
         if (active) {
             if (!have) { sim_cur = *simblk_at(SB, lane, n); bc_cur = bthk[(size_t) (n + 1) * 3]; be_cur = bthk[(size_t) (n + 1) * 3 + 2]; }
             if (n + 1 < hi) { sim_nx = *simblk_at(SB, lane, n + 1); bc_nx = bthk[(size_t) (n + 2) * 3]; be_nx = bthk[(size_t) (n + 2) * 3 + 2]; }
         }
         st_prev = n0 + 1 < hi0 && n0 + 2 <= c1;
-        if (st_prev) { need(n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
+        if (st_prev) { strip_need<V7Strip>(S, n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
         RS myH = oH, myG = oG, myG2 = oG2;
         if (active) {
             const bool do_hori = n > b.left;
@@ -246,20 +215,18 @@ __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const 
     }
     if (p_act) trace[p_tri] = (uint8_t) p_trb;
     if (wr_rows) flush_rows(cbase + nsteps - 1 - llast);
-    publish(0xFFFFF);
+    strip_publish<V7Strip>(S, 0xFFFFF);
 }
 
+#define V7_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
+NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr)
 #define V7_KERNEL(NAME, N3)                                                                         \
-extern "C" __global__ void __launch_bounds__(64)                                                    \
-NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr) \
+V7_SIG(NAME, __launch_bounds__(64))                                                                 \
 {                                                                                                   \
     __shared__ __attribute__((aligned(16))) unsigned v7_lds[64 + 32];                               \
     li32 *s_vals = (li32 *) ((lchar *) v7_lds + 128);                                               \
     for (;;) {                                                                                      \
-        s_vals[threadIdx.x] = atomicAdd(qhead, threadIdx.x == 0 ? 1 : 0);                           \
-        __syncthreads();                                                                            \
-        const int t = __builtin_amdgcn_readfirstlane(s_vals[0]);                                    \
-        __syncthreads();                                                                            \
+        const int t = strip_pop(qhead, s_vals);                                                     \
         if (t >= ntiles) break;                                                                     \
         const V2Tile T = tiles[t];                                                                  \
         if (T.ti < 0) {           /* a boundary chain */                                            \
@@ -268,15 +235,7 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
             continue;                                                                               \
         }                                                                                           \
         int *failp = done + done[G2G_HDR + 2] + T.prob;                                             \
-        if (threadIdx.x == 0) s_vals[0] = g2g_dp_failed(failp) ? 1 : 0;                             \
-        __syncthreads();                                                                            \
-        const int dp_dead = s_vals[0];                                                              \
-        __syncthreads();                                                                            \
-        if (dp_dead) {                                                                              \
-            if (threadIdx.x == 0) G2G_POST(done + T.self, ((gen & 0x7FF) << 20) | 0xFFFFF); \
-            __syncthreads();                                                                        \
-            continue;                                                                               \
-        }                                                                                           \
+        if (strip_dp_dead(failp, s_vals)) { strip_release(done + T.self, strip_done_word(gen)); continue; } \
         const int *pl = T.dep_left >= 0 ? done + T.dep_left : (const int *) 0;                      \
         const int *pu = T.dep_up >= 0 ? done + T.dep_up : (const int *) 0;                          \
         v7_strip<N3>(probs[T.prob], (lchar *) v7_lds, T.ti, T.nsteps, pu, done + T.self, done + G2G_HDR, gen, pint, pl, \
@@ -289,5 +248,5 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
 V7_KERNEL(g2g_v7_ngp2, false)
 V7_KERNEL(g2g_v7_ngp3, true)
 #else
-extern "C" __global__ void g2g_v7_ngp2(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr); extern "C" __global__ void g2g_v7_ngp3(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr);
+V7_SIG(g2g_v7_ngp2, ); V7_SIG(g2g_v7_ngp3, );
 #endif

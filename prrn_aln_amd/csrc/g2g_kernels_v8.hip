@@ -277,27 +277,10 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
         r.val = *(const lf64 *) q; r.dir = (int) q[2]; r.glb = 0;
         _Pragma("unroll") for (int k = 0; k < 6; ++k) l.g[k] = (int) q[4 + k];
     };
-    int avail = prog_up ? 0 : 0x7fffffff;
-    const int penc = (pgen & 0x7FF) << 20;
-    auto need = [&](const int col) {                       // wave-uniform: every lane polls, nobody branches alone
-        const int want = penc | (col < 0xFFFFF ? col : 0xFFFFF);
-        if (prog_up && want > avail) {
-            avail = g2g_wait_ge(prog_up, want, dbg, failp, ti);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    };
-    auto publish = [&](const int col) {
-        if (prog_self) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            G2G_POST(prog_self, penc | (col < 0 ? 0 : col < 0xFFFFF ? col : 0xFFFFF));
-        }
-    };
+    StripSync S = strip_sync(prog_up, prog_self, dbg, failp, pgen, ti);
     for (int k = lane; k < 7 * V8_REC; k += 64) stsc[k] = 0;
     team_sync();
-    need(cbase + 1 <= c1 ? cbase + 1 : cbase);
+    strip_need<StripTraits>(S, cbase + 1 <= c1 ? cbase + 1 : cbase);     // (StripTraits: the defaults; and no strip_where)
     {
         unsigned rh = 0, rg = 0, rg2 = 0;
         stage_load(cbase, false, rh, rg, rg2);
@@ -345,7 +328,7 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
         if (st_prev) stage_store(n0 + 1, vert0, st_h, st_g, st_g2);
         if (p_act) trace[p_tri] = (uint8_t) p_trb;
         if (wr_rows && s > 0) flush_rows(n0 - 1 - llast);
-        if (prog_self && s > 0 && (s & (pint - 1)) == 0) publish(n0 - llast);
+        if (prog_self && s > 0 && (s & (pint - 1)) == 0) strip_publish<StripTraits>(S, n0 - llast);
         if ((s & 63) == 0) { simblk_fill(P, SB, (s >> 6) + 1, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         hd = hu; lhd = lhu;
         hu = rs_up(oH); gu = rs_up(oG); lhu = nl_up(lH); lgu = nl_up(lG);
@@ -369,7 +352,7 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
             if (n + 1 < hi) { sim_nx = *simblk_at(SB, lane, n + 1); bc_nx = bthk[(size_t) (n + 2) * 3]; v8_load_pos(Bnx, b, n + 1, bn); }
         }
         st_prev = n0 + 1 < hi0 && n0 + 2 <= c1;
-        if (st_prev) { need(n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
+        if (st_prev) { strip_need<StripTraits>(S, n0 + 2); stage_load(n0 + 2, vert0, st_h, st_g, st_g2); }
         RS myH = oH, myG = oG, myG2 = oG2;
         NL nH = lH, nG = lG, nG2 = lG2;
         if (active) {
@@ -425,20 +408,18 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
     }
     if (p_act) trace[p_tri] = (uint8_t) p_trb;
     if (wr_rows) flush_rows(cbase + nsteps - 1 - llast);
-    publish(0xFFFFF);
+    strip_publish<StripTraits>(S, 0xFFFFF);
 }
 
+#define V8_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
+NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr)
 #define V8_KERNEL(NAME, N3)                                                                         \
-extern "C" __global__ void __launch_bounds__(64)                                                    \
-NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr) \
+V8_SIG(NAME, __launch_bounds__(64))                                                                 \
 {                                                                                                   \
     __shared__ __attribute__((aligned(16))) unsigned v8_lds[96 + 64];                               \
     li32 *s_vals = (li32 *) ((lchar *) v8_lds + 384);                                               \
     for (;;) {                                                                                      \
-        s_vals[threadIdx.x] = atomicAdd(qhead, threadIdx.x == 0 ? 1 : 0);                           \
-        __syncthreads();                                                                            \
-        const int t = __builtin_amdgcn_readfirstlane(s_vals[0]);                                    \
-        __syncthreads();                                                                            \
+        const int t = strip_pop(qhead, s_vals);                                                     \
         if (t >= ntiles) break;                                                                     \
         const V2Tile T = tiles[t];                                                                  \
         if (T.ti < 0) {           /* a boundary chain */                                            \
@@ -447,15 +428,7 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
             continue;                                                                               \
         }                                                                                           \
         int *failp = done + done[G2G_HDR + 2] + T.prob;                                             \
-        if (threadIdx.x == 0) s_vals[0] = g2g_dp_failed(failp) ? 1 : 0;                             \
-        __syncthreads();                                                                            \
-        const int dp_dead = s_vals[0];                                                              \
-        __syncthreads();                                                                            \
-        if (dp_dead) {                                                                              \
-            if (threadIdx.x == 0) G2G_POST(done + T.self, ((gen & 0x7FF) << 20) | 0xFFFFF); \
-            __syncthreads();                                                                        \
-            continue;                                                                               \
-        }                                                                                           \
+        if (strip_dp_dead(failp, s_vals)) { strip_release(done + T.self, strip_done_word(gen)); continue; } \
         const int *pl = T.dep_left >= 0 ? done + T.dep_left : (const int *) 0;                      \
         const int *pu = T.dep_up >= 0 ? done + T.dep_up : (const int *) 0;                          \
         v8_strip<N3>(probs[T.prob], (lchar *) v8_lds, T.ti, T.nsteps, pu, done + T.self, done + G2G_HDR, gen, pint, pl, \
@@ -468,5 +441,5 @@ NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *don
 V8_KERNEL(g2g_v8_ntv2, false)
 V8_KERNEL(g2g_v8_ntv3, true)
 #else
-extern "C" __global__ void g2g_v8_ntv2(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr); extern "C" __global__ void g2g_v8_ntv3(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr);
+V8_SIG(g2g_v8_ntv2, ); V8_SIG(g2g_v8_ntv3, );
 #endif

@@ -8,6 +8,7 @@
 #include "g2g_device.h"
 #include "g2g_internal.h"
 #include "g2g_kernels.hip"
+#include "g2g_strip.h"
 #include "g2g_kernels_v2.hip"
 #ifdef G2G_V2_STAMP
 // diagnostics build (G2G_EXTRA_FLAGS=-DG2G_V2_STAMP): s_memtime per phase of the v2 step loop, summed over the first lane of every

@@ -8,5 +8,6 @@
 #include "g2g_device.h"
 #include "g2g_internal.h"
 #include "g2g_kernels.hip"
+#include "g2g_strip.h"
 #include "g2g_kernels_v2.hip"
 #include "g2g_kernels_v3.hip"

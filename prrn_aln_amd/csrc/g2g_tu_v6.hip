@@ -8,6 +8,7 @@
 #include "g2g_device.h"
 #include "g2g_internal.h"
 #include "g2g_kernels.hip"
+#include "g2g_strip.h"
 #include "g2g_kernels_v2.hip"
 #include "g2g_kernels_v3.hip"
 #include "g2g_kernels_v6.hip"
