@@ -133,7 +133,9 @@ typedef struct g2g_problem {
     g2g_side a, b;
     double   spb_fact;              /* SpbFact = alprm.scale * alprm2.spb (src/gsinfo.cc:35): weight of the intron-position bonus
                                        PfqItr::match_score adds in forwardB (src/fwd2c.h:378-379,446-452,472) when BOTH sides are
-                                       annotated; 0 switches it off.  DPs with the bonus run on g2g_forward_kernel.            */
+                                       annotated; 0 switches it off.  DPs with the bonus run on the bonus-aware strip kernels
+                                       (DPunit: v7, _hf / _pf: v2) or on g2g_forward_kernel (_nv, option NO_STRIP_BONUS):
+                                       g2g_batch_paths tells which.                                                            */
 } g2g_problem;
 
 /* result of one DP */
@@ -190,6 +192,16 @@ int       g2g_batch_fetch(g2g_batch *b, g2g_result *res);
 void      g2g_batch_times(const g2g_batch *b, float *fwd_ms, float *tb_ms);
 long long g2g_batch_cells(const g2g_batch *b);
 size_t    g2g_batch_arena_bytes(const g2g_batch *b);
+/* Which kernel generation each of the batch's n problems runs on: gen[i] = 1 (g2g_forward_kernel: one workgroup per DP,
+   state in HBM), 2 (8-lanes-per-cell strips), 3 (v3 / v3r), 6, 7 or 8; 0 for a problem that was
+   refused (g2g_result::status).  After g2g_batch_prepare: the kernel chosen.  After g2g_batch_run: the kernel that
+   produced the result g2g_batch_fetch returns -- a DP re-run after a lost wait reports the kernel of its successful
+   re-run.  G2G_ERR_ARG for a NULL argument.  (An entry point added without a change of g2g_abi_version.) */
+int       g2g_batch_paths(const g2g_batch *b, int32_t *gen);
+/* The cells of a problem that receive the intron-position bonus, as g2g_batch_prepare tabulates them (host only, needs no
+   device): row-major, n ascending within a row; h is added to H of cell (m, n), mx to its best non-diagonal record.  Writes
+   up to cap entries into each non-NULL array and returns the number of cells (0: no bonus), or G2G_ERR_ARG. */
+int       g2g_bonus_cells(const g2g_problem *p, int cap, int32_t *m, int32_t *n, double *h, double *mx);
 /* The scheduler's waits are bounded by wall clock: a wait that runs into the limit costs its DP a re-run
    inside g2g_batch_run, and the results stay complete.  These two make every such event visible: for the LAST run of a
    batch the number of waits that gave up and of DPs re-run (and the DPs re-run over the batch's life); for a context

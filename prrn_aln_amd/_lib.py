@@ -46,6 +46,8 @@ def lib():
     L.g2g_batch_cells.argtypes = [C.c_void_p]
     L.g2g_batch_arena_bytes.restype = C.c_size_t
     L.g2g_batch_arena_bytes.argtypes = [C.c_void_p]
+    L.g2g_batch_paths.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.g2g_bonus_cells.argtypes = [C.POINTER(_abi.Problem), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _abi.c_f64p, _abi.c_f64p]
     L.g2g_batch_free.argtypes = [C.c_void_p]
     L.g2g_batch_recovery.restype = None
     L.g2g_batch_recovery.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -329,6 +329,14 @@ struct Blob {                       // host image of the input part of the arena
         p = q; cap = c;
     }
     void extend(size_t newsize) { if (newsize <= sz) return; grow(newsize); if (oom) return; memset(p + sz, 0, newsize - sz); sz = newsize; }
+    size_t put_now(const void *src, size_t bytes)      // put() of a source that does not live until flush(): copied here, whatever its size
+    {
+        const size_t off = put(0, 0);
+        extend(off + bytes);
+        if (oom) return 0;
+        if (bytes) memcpy(p + off, src, bytes);
+        return off;
+    }
     size_t put(const void *src, size_t bytes)
     {
         const size_t off = (sz + 15) & ~(size_t) 15;
@@ -363,6 +371,12 @@ struct Blob {                       // host image of the input part of the arena
 // the problem index of a batch sits in a grid y / z dimension of some launches (limit 65535)
 #define G2G_MAX_BATCH 32768
 extern "C" void g2g_batch_free(g2g_batch *b);
+// Variant slots (one queue, one persistent launch each).  [0, G2G_HDR): the kernels without a bonus table, their queue heads
+// are the first G2G_HDR words of d_flags (g2g_strip.h).  [G2G_HDR, G2G_NVAR): the bonus-aware instantiations -- g2g_v7_ngp{2,3}_ib
+// at 24 / 25, g2g_v2_{hf2,hf3,pf2,pf3}_ib at 26 .. 29 (odd slots: Noll 3, as below); their heads live at d_flags + xq_off.
+#define G2G_NVAR (G2G_HDR + 6)
+static inline bool slot_v7ib(int v) { return v >= G2G_HDR && v < G2G_HDR + 2; }
+static inline bool slot_v2ib(int v) { return v >= G2G_HDR + 2 && v < G2G_NVAR; }
 struct g2g_batch {
     g2g_ctx *ctx;
     int n;
@@ -388,8 +402,8 @@ struct g2g_batch {
     size_t simtile_lds;             // LDS of the tiled column-score kernel
     size_t tiles_cap, flags_cap;    // pool blocks behind d_tiles / d_flags
     V2Tile *d_tiles;                // tiles: per variant (v2: hf2, hf3, pf2, pf3; v3: the same four) a queue ordered by wavefront i + j
-    int var_off[25];                // variant v owns tiles [var_off[v], var_off[v+1])
-    long long var_cells[24];        // in-band cells of the DPs of variant v (the CU shares of a run are proportional to cells x cost)
+    int var_off[G2G_NVAR + 1];      // variant v owns tiles [var_off[v], var_off[v+1])
+    long long var_cells[G2G_NVAR];       // in-band cells of the DPs of variant v (the CU shares of a run are proportional to cells x cost)
     V3Lds v3lds[8];                 // LDS plan of the v3 variants
     V6Lds v6lds[6];                 // LDS plans of the v6 (_pf, one lane per cell, rank-form merges) launches: Noll 2, 3 x footprint class A / B / C
     int v2_cols;
@@ -402,12 +416,15 @@ struct g2g_batch {
     std::vector<int> flags0;        // initial contents of d_flags (re-uploaded when the 11-bit generation of the progress counters wraps)
     long long ntiles;
     float fwd_ms, tb_ms;
-    double *simscr[24]; size_t simscr_cap[24];
+    double *simscr[G2G_NVAR]; size_t simscr_cap[G2G_NVAR];
     unsigned *twin[6]; size_t twin_cap[6];       // per v6 launch: HBM image of the dynamic lists' parts beyond their inline LDS slots
     bool v6_on;                     // this batch is large enough for v6 (else its _pf DPs go to v2: shorter critical path)
     int hdr_img[G2G_HDR + G2G_HDRN];       // host image of the queue heads + wait header of the current run
     std::vector<const g2g_problem *> src;        // the caller's problems (kept alive by the caller until the batch is freed): a DP
                                                  // that lost a wait is re-run from here on the non-polling kernel
+    std::vector<char> ib;                        // per problem: runs on a bonus-aware strip kernel (g2g_v7_*_ib / g2g_v2_*_ib)
+    std::vector<int> path_rec;                   // kernel generation of a recovered DP's successful re-run (g2g_batch_paths)
+    int xq_off;                                  // offset in d_flags of the queue heads of the variant slots G2G_HDR .. G2G_NVAR - 1
     int fail_off;                                // offset of the per-DP fail flags in d_flags
     int dump_off;                                // offset of the time-out dump area in d_flags (0: none)
     int n_recovered;                             // DPs re-run after a time-out, over the life of the batch
@@ -686,6 +703,20 @@ static void intron_bonus_table(const g2g_problem *p, std::vector<BonusCell> &out
     }
 }
 
+extern "C" int g2g_bonus_cells(const g2g_problem *p, int cap, int32_t *m, int32_t *n, double *h, double *mx)
+{
+    if (!p || cap < 0) { g2g_set_error("g2g_bonus_cells: %s", "bad argument"); return G2G_ERR_ARG; }
+    std::vector<BonusCell> bc;
+    if (!is_rect(p->alnmode)) intron_bonus_table(p, bc);
+    for (size_t k = 0; k < bc.size() && k < (size_t) cap; ++k) {
+        if (m) m[k] = bc[k].m;
+        if (n) n[k] = bc[k].n;
+        if (h) h[k] = bc[k].h;
+        if (mx) mx[k] = bc[k].mx;
+    }
+    return (int) bc.size();
+}
+
 static void rebase_side(DevSide &d, char *base)
 {
     rebase(d.seq, base); rebase(d.weight, base); rebase(d.pseq, base); rebase(d.thk, base);
@@ -723,12 +754,12 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
     };
     g2g_batch *b = new g2g_batch();
     b->ctx = ctx; b->n = n; b->d_arena = 0; b->d_probs = 0; b->fwd_ms = b->tb_ms = 0;
-    for (int k = 0; k < 24; ++k) { b->simscr[k] = 0; b->simscr_cap[k] = 0; }
+    for (int k = 0; k < G2G_NVAR; ++k) { b->simscr[k] = 0; b->simscr_cap[k] = 0; }
     for (int k = 0; k < 6; ++k) { b->twin[k] = 0; b->twin_cap[k] = 0; }
     b->src.assign(prob, prob + n); b->fail_off = 0; b->dump_off = 0; b->force_v1 = force_v1; b->is_retry = false; b->n_recovered = 0;
-    b->recovered.assign(n, g2g_result()); b->was_recovered.assign(n, 0);
+    b->recovered.assign(n, g2g_result()); b->was_recovered.assign(n, 0); b->ib.assign(n, 0); b->path_rec.assign(n, 0); b->xq_off = 0;
     b->nsimmat = 0; b->injected = g2g_opt(ctx, "INJECT_STALL") != 0;
-    for (int k = 0; k < 24; ++k) b->var_cells[k] = 0;
+    for (int k = 0; k < G2G_NVAR; ++k) b->var_cells[k] = 0;
     b->last_timeouts = b->last_recovered = 0;
     b->v3_cols = 128; b->v2_cols = G2G_V2_TILE_COLS;
 
@@ -785,10 +816,21 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
                 std::vector<int> bm, bn; std::vector<double> bh, bx;
                 for (const BonusCell &c : bc) { bm.push_back(c.m); bn.push_back(c.n); bh.push_back(c.h); bx.push_back(c.mx); }
                 d.nbonus = (int) bc.size();
-                d.bon_m = OFF<const int>(bl.put(bm.data(), sizeof(int) * bm.size()));
-                d.bon_n = OFF<const int>(bl.put(bn.data(), sizeof(int) * bn.size()));
-                d.bon_h = OFF<const double>(bl.put(bh.data(), sizeof(double) * bh.size()));
-                d.bon_mx = OFF<const double>(bl.put(bx.data(), sizeof(double) * bx.size()));
+                // the per-row index of the strip kernels behind bon_m's entries: first entry of row a.left + r, r = 0 .. rows
+                // (the table is row-major with n ascending within a row; g2g_forward_kernel reads the first nbonus entries only)
+                {
+                    const int rows = p->a.right - p->a.left;
+                    size_t k = 0;
+                    for (int r = 0; r <= rows; ++r) {
+                        while (k < bc.size() && bc[k].m < p->a.left + r) ++k;
+                        bm.push_back((int) k);
+                    }
+                }
+                // (put_now: the four vectors are gone by the time flush() makes put()'s deferred copies)
+                d.bon_m = OFF<const int>(bl.put_now(bm.data(), sizeof(int) * bm.size()));
+                d.bon_n = OFF<const int>(bl.put_now(bn.data(), sizeof(int) * bn.size()));
+                d.bon_h = OFF<const double>(bl.put_now(bh.data(), sizeof(double) * bh.size()));
+                d.bon_mx = OFF<const double>(bl.put_now(bx.data(), sizeof(double) * bx.size()));
             }
         }
     }
@@ -905,7 +947,20 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
                 else if (v2fit) d.v2_ok = 1;
             }
         }
-        if (d.nbonus) d.v2_ok = 0;               // the intron-position bonus lives in g2g_forward_kernel only
+        if (d.nbonus) {
+            // The intron-position bonus: g2g_forward_kernel (v1), and the bonus-aware instantiations of the strips without gap
+            // state (v7) and of the 8-lanes-per-cell strips (v2, sweep mode) -- not v3 / v3r / v6 (register-bound) and not v8, so an
+            // annotated _hf / _pf DP goes to v2 whatever would otherwise have claimed it, within v2's own limits, and _nv stays
+            // on v1.  NO_STRIP_BONUS: v1 for all of them, as before the strips knew the bonus.
+            const int was = d.v2_ok;
+            d.v2_ok = 0;
+            if (!g2g_opt(ctx, "NO_STRIP_BONUS")) {
+                if (was == 7) d.v2_ok = 7;
+                else if (was >= 1 && was <= 6 && (d.kind == 1 || d.kind == 2) && b->v2_sweep && std::max(p->a.len, p->b.len) < 32768 &&
+                         v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, b->v2_threads) + 4 * b->v2_threads <= V2_LDS_MAX) d.v2_ok = 1;
+            }
+            b->ib[i] = d.v2_ok ? 1 : 0;
+        }
         if (!d.v2_ok) v1_state();
         else {                                  // g2g_spscore_kernel keeps its two dynamic lists in dla/dlb[XH] (stride spw)
             d.spw = 1;
@@ -987,9 +1042,9 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
     // ordered by wavefront i + j; one completion flag per tile slot (empty slots count as done for ever)
     b->d_tiles = 0; b->tiles_cap = b->flags_cap = 0; b->d_idxp = 0; b->np = 0; b->ntiles = 0; b->lds2p = 0; b->v2_maxrows = 1; b->v2_maxcols = 1; b->simtile_lds = 0; b->d_flags = 0; b->nflags = 0; b->gen = 0;
     {
-        std::vector<std::vector<std::vector<V2Tile> > > q(G2G_HDR);   // [variant][wavefront] -> tiles
+        std::vector<std::vector<std::vector<V2Tile> > > q(G2G_NVAR);  // [variant][wavefront] -> tiles
         std::vector<int> flags(G2G_HDR + G2G_HDRN, 0);           // queue heads, then the header of the waits (g2g_wait_ge)
-        std::vector<V2Tile> pre[G2G_HDR];                 // boundary chains of sweep-mode DPs: they head their variant's queue
+        std::vector<V2Tile> pre[G2G_NVAR];                // boundary chains of sweep-mode DPs: they head their variant's queue
         std::vector<int> ip;                              // the other DPs: chains in the prologue kernel
         const bool chainq = !g2g_opt(ctx, "NO_CHAINQ");
         int v6rows[6] = {0, 0, 0, 0, 0, 0}, v6ca4[6] = {0, 0, 0, 0, 0, 0};
@@ -1017,7 +1072,7 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
             //  or a handful of balanced divisions would cost every strip of the sweep its occupancy)
             int v6cls = 0;
             if (d.v2_ok == 6) { const int tot = v6_layout(v6_rows_bytes(d), (d.capa + 3) & ~3, v6_ring_need(prob[i])).total; v6cls = (d.noll == 3 ? 1 : 0) + (tot > V6_SMALL_LDS ? 4 : tot > V6_CLASS_A ? 2 : 0); }
-            const int var = d.v2_ok == 8 ? 18 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 7 ? 16 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 6 ? v6_slot(v6cls) : (d.v2_ok - 1) * 4 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0);
+            const int var = b->ib[i] ? (d.v2_ok == 7 ? G2G_HDR + (d.noll == 3 ? 1 : 0) : G2G_HDR + 2 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0)) : d.v2_ok == 8 ? 18 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 7 ? 16 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 6 ? v6_slot(v6cls) : (d.v2_ok - 1) * 4 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0);
             b->var_cells[var] += b->cells[i];
             if (d.v2_ok == 6) {
                 v6rows[v6cls] = std::max(v6rows[v6cls], v6_rows_bytes(d));
@@ -1069,12 +1124,12 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
             }
         }
         std::vector<V2Tile> all;
-        for (int v = 0; v < G2G_HDR; ++v) {
+        for (int v = 0; v < G2G_NVAR; ++v) {
             b->var_off[v] = (int) all.size();
             all.insert(all.end(), pre[v].begin(), pre[v].end());
             for (size_t k = 0; k < q[v].size(); ++k) all.insert(all.end(), q[v][k].begin(), q[v][k].end());
         }
-        b->var_off[G2G_HDR] = (int) all.size();
+        b->var_off[G2G_NVAR] = (int) all.size();
         for (int v = 0; v < 6; ++v) b->v6lds[v] = v6_layout(v6rows[v], v6ca4[v], v6rs[v]);
         for (int v = 0; v < 8; ++v) b->v3lds[v] = v3_layout(need[v].rows_bytes, need[v].ca4, need[v].apool, need[v].bpool, b->v3_cols);
         // test hook: G2G_INJECT_STALL=<i> makes the first strip / tile of problem i depend on a flag nobody ever writes
@@ -1089,6 +1144,8 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
         flags.resize(flags.size() + (size_t) (n > 0 ? n : 1), 0);
         b->dump_off = (int) flags.size();                 // the first time-out's view of its whole DP (g2g_wait_ge: G2G_DUMP_STRIPS strips x 7 words)
         flags.resize(flags.size() + 2 + G2G_DUMP_WORDS * G2G_DUMP_STRIPS, 0);
+        b->xq_off = (int) flags.size();                   // queue heads of the bonus-aware variants
+        flags.resize(flags.size() + (G2G_NVAR - G2G_HDR), 0);
         b->ntiles = (long long) all.size();
         b->nflags = (int) flags.size();
         b->flags0 = flags;
@@ -1156,6 +1213,8 @@ static hipStream_t cu_share_stream(g2g_ctx *c, int lo, int n)
 static double variant_cost(int v)
 {
     const double n3 = (v & 1) ? 1.4 : 1.0;                  // odd slots: Noll 3
+    if (slot_v7ib(v)) return 0.8 * n3;                      // the bonus-aware instantiations: as their kernels
+    if (slot_v2ib(v)) return (v < G2G_HDR + 4 ? 2.0 : 5.0) * n3;
     if (v < 2) return 2.0 * n3;                             // v2 _hf
     if (v < 4) return 5.0 * n3;                             // v2 _pf
     if (v < 8) return 2.5 * n3;                             // v3 with LDS lists
@@ -1163,6 +1222,14 @@ static double variant_cost(int v)
     if (v < 16 || v >= 20) return 2.7 * n3;                 // v6
     if (v < 18) return 0.8 * n3;                            // v7
     return 1.2 * n3;                                        // v8
+}
+
+static int batch_path(const g2g_batch *b, int i)
+{
+    if (b->status[i]) return 0;
+    if (b->was_recovered[i]) return b->path_rec[i];
+    const int k = b->dp[i].v2_ok;
+    return k == 0 ? 1 : k == 1 ? 2 : k <= 3 ? 3 : k;
 }
 
 // Compact the valid problems to the front?  No: invalid ones keep kind = -1 and the kernels skip them.
@@ -1212,7 +1279,8 @@ extern "C" int g2g_batch_run(g2g_batch *b)
         if (g2g_opt(ctx, "DEBUG")) { hipError_t e3 = hipStreamSynchronize(ctx->stream); fprintf(stderr, "[g2g] prologue+sim done: %s\n", hipGetErrorString(e3)); fflush(stderr); }
         // persistent tile / strip kernels: one launch per kernel variant, each on its own stream (they are independent)
         typedef void (*v2k_t)(const DevProb *, const V2Tile *, int, int *, int *, int, int, int, int, int, double *);
-        static const v2k_t v2k[4] = {g2g_v2_hf2, g2g_v2_hf3, g2g_v2_pf2, g2g_v2_pf3};
+        static const v2k_t v2k[8] = {g2g_v2_hf2, g2g_v2_hf3, g2g_v2_pf2, g2g_v2_pf3, g2g_v2_hf2_ib, g2g_v2_hf3_ib, g2g_v2_pf2_ib, g2g_v2_pf3_ib};
+        auto qhead = [&](int slot) -> int * { return slot < G2G_HDR ? b->d_flags + slot : b->d_flags + b->xq_off + (slot - G2G_HDR); };
         typedef void (*v3k_t)(const DevProb *, const V2Tile *, int, int *, int *, int, V3Lds, int, int, int, double *);
         static const v3k_t v3k[8] = {g2g_v3_hf2, g2g_v3_hf3, 0, 0, g2g_v3r_hf2, g2g_v3r_hf3, 0, 0};       // (_pf strips: g2g_v6_*, below)
         // one persistent launch per variant, each on its own stream (they are independent of each other)
@@ -1235,6 +1303,7 @@ extern "C" int g2g_batch_run(g2g_batch *b)
             hdr[G2G_HDR + 3] = (int) std::min(2.0e9, limit_ms * ctx->rt_ticks_per_ms / 65536.) + 1;
             HIPCHK(hipMemcpyAsync(b->d_flags, hdr, sizeof b->hdr_img, hipMemcpyHostToDevice, ctx->stream));
             HIPCHK(hipMemsetAsync(b->d_flags + b->fail_off, 0, sizeof(int) * (size_t) (b->n > 0 ? b->n : 1), ctx->stream));
+            HIPCHK(hipMemsetAsync(b->d_flags + b->xq_off, 0, sizeof(int) * (G2G_NVAR - G2G_HDR), ctx->stream));
         }
         HIPCHK(hipEventRecord(ctx->vev[G2G_NVS], ctx->stream));
         int nlaunch = 0;                                      // every persistent launch of this run takes the next stream
@@ -1250,22 +1319,23 @@ extern "C" int g2g_batch_run(g2g_batch *b)
             return b->simscr[slot];
         };
         // ---- CU shares of this run's persistent launches (cu_share_stream) ----
-        int sh_lo[G2G_HDR], sh_n[G2G_HDR];
-        hipStream_t sh_stream[G2G_HDR];
-        for (int v = 0; v < G2G_HDR; ++v) sh_stream[v] = 0;
+        int sh_lo[G2G_NVAR], sh_n[G2G_NVAR];
+        hipStream_t sh_stream[G2G_NVAR];
+        for (int v = 0; v < G2G_NVAR; ++v) sh_stream[v] = 0;
         bool shares = false;
         {
             const int T2s = b->v2_threads;
             auto wpc_of = [&](int v) -> int {                 // resident workgroups per CU of variant slot v
-                if (v < 4) return std::max(1, std::min(2048 / T2s, (int) (V2_LDS_MAX / (b->lds2 + 4 * (size_t) T2s))));
+                if (slot_v7ib(v)) return 16;
+                if (v < 4 || slot_v2ib(v)) return std::max(1, std::min(2048 / T2s, (int) (V2_LDS_MAX / (b->lds2 + 4 * (size_t) T2s))));
                 if (v < 12) { const int t = b->v3lds[v - 4].total; return t > 0 ? std::max(1, std::min(16, (int) (V2_LDS_MAX / (size_t) t))) : 1; }
                 if (v < 16 || v >= 20) { const int cls = v < 16 ? v - 12 : v - 16; const int t = b->v6lds[cls].total; return t > 0 ? std::max(1, std::min(4, (int) (V2_LDS_MAX / (size_t) t))) : 1; }
                 return v < 18 ? 16 : 4;
             };
-            double work[G2G_HDR], tot = 0;
-            int need[G2G_HDR], nl = 0;
+            double work[G2G_NVAR], tot = 0;
+            int need[G2G_NVAR], nl = 0;
             double demand = 0;
-            for (int v = 0; v < G2G_HDR; ++v) {
+            for (int v = 0; v < G2G_NVAR; ++v) {
                 const int cnt = b->var_off[v + 1] - b->var_off[v];
                 work[v] = cnt ? (double) std::max<long long>(b->var_cells[v], 1) * variant_cost(v) : 0;
                 need[v] = cnt ? std::min(32, std::max(1, (cnt + 8 * wpc_of(v) - 1) / (8 * wpc_of(v)))) : 0;   // units its tiles can occupy
@@ -1288,12 +1358,12 @@ extern "C" int g2g_batch_run(g2g_batch *b)
             if (want && ncu == 256 && nl >= 2 && nl <= (int) mstream_cap(ctx) && (force || demand >= 2.0 * ncu) && tot > 0 && !g2g_opt(ctx, "DEBUG")) {      // (256 CUs in 8 XCDs: the mask layout the shares are written for)
                 int left = 32;
                 double wleft = tot;
-                bool done[G2G_HDR];
-                for (int v = 0; v < G2G_HDR; ++v) done[v] = work[v] == 0;
+                bool done[G2G_NVAR];
+                for (int v = 0; v < G2G_NVAR; ++v) done[v] = work[v] == 0;
                 // launches whose tiles cannot fill their proportional share take what they can fill; the rest is re-divided
-                for (int round = 0; round < G2G_HDR; ++round) {
+                for (int round = 0; round < G2G_NVAR; ++round) {
                     bool changed = false;
-                    for (int v = 0; v < G2G_HDR; ++v) {
+                    for (int v = 0; v < G2G_NVAR; ++v) {
                         if (done[v]) continue;
                         const double prop = wleft > 0 ? left * work[v] / wleft : 0;
                         if (need[v] <= prop) { sh_n[v] = need[v]; left -= need[v]; wleft -= work[v]; done[v] = true; changed = true; }
@@ -1301,11 +1371,11 @@ extern "C" int g2g_batch_run(g2g_batch *b)
                     if (!changed) break;
                 }
                 int open_ = 0;
-                for (int v = 0; v < G2G_HDR; ++v) if (!done[v]) ++open_;
+                for (int v = 0; v < G2G_NVAR; ++v) if (!done[v]) ++open_;
                 if (left >= open_) {
                     int given = 0;
-                    double frac[G2G_HDR];
-                    for (int v = 0; v < G2G_HDR; ++v) {
+                    double frac[G2G_NVAR];
+                    for (int v = 0; v < G2G_NVAR; ++v) {
                         frac[v] = -1;
                         if (done[v]) continue;
                         const double prop = left * work[v] / wleft;
@@ -1315,13 +1385,13 @@ extern "C" int g2g_batch_run(g2g_batch *b)
                     }
                     while (given < left) {                       // largest remainders first
                         int best = -1;
-                        for (int v = 0; v < G2G_HDR; ++v) if (frac[v] >= 0 && (best < 0 || frac[v] > frac[best])) best = v;
+                        for (int v = 0; v < G2G_NVAR; ++v) if (frac[v] >= 0 && (best < 0 || frac[v] > frac[best])) best = v;
                         if (best < 0) break;
                         ++sh_n[best]; frac[best] = -0.5; ++given;
                     }
                     while (given > left) {                       // (the minimum of one unit each overdrew: take from the largest)
                         int big = -1;
-                        for (int v = 0; v < G2G_HDR; ++v) if (!done[v] && sh_n[v] > 1 && (big < 0 || sh_n[v] > sh_n[big])) big = v;
+                        for (int v = 0; v < G2G_NVAR; ++v) if (!done[v] && sh_n[v] > 1 && (big < 0 || sh_n[v] > sh_n[big])) big = v;
                         if (big < 0) break;
                         --sh_n[big]; --given;
                     }
@@ -1330,7 +1400,7 @@ extern "C" int g2g_batch_run(g2g_batch *b)
                         // as good, and keeps the number of queues down
                         if (nl == 2) {
                             int v0 = -1, v1 = -1;
-                            for (int v = 0; v < G2G_HDR; ++v) if (sh_n[v]) { if (v0 < 0) v0 = v; else v1 = v; }
+                            for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v]) { if (v0 < 0) v0 = v; else v1 = v; }
                             if (v0 >= 0 && v1 >= 0 && sh_n[v0] + sh_n[v1] == 32) {
                                 // (once the context holds its fill of shares, the nearest one is taken whatever the distance: creating and
                                 //  destroying queues while launches are resident makes the scheduler rebuild its run list, which the waiting
@@ -1355,16 +1425,16 @@ extern "C" int g2g_batch_run(g2g_batch *b)
                         // 5 whole refinements (4360 windows) without an event against 0.6 events per run before, 0.5 % slower.
                         // NO_SHARE_GAP restores adjacent shares.
                         const int gap = (!g2g_opt(ctx, "NO_SHARE_GAP") && nl == 2) ? 1 : 0;
-                        if (gap) { int vb = -1; for (int v = 0; v < G2G_HDR; ++v) if (sh_n[v] && (vb < 0 || sh_n[v] > sh_n[vb])) vb = v; if (vb >= 0 && sh_n[vb] > 2) --sh_n[vb]; }
+                        if (gap) { int vb = -1; for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v] && (vb < 0 || sh_n[v] > sh_n[vb])) vb = v; if (vb >= 0 && sh_n[vb] > 2) --sh_n[vb]; }
                         bool first = true;
-                        for (int v = 0; v < G2G_HDR; ++v) if (sh_n[v]) { if (!first) lo += gap; first = false; sh_lo[v] = lo; lo += sh_n[v]; sh_stream[v] = cu_share_stream(ctx, sh_lo[v], sh_n[v]); if (!sh_stream[v]) shares = false; }
+                        for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v]) { if (!first) lo += gap; first = false; sh_lo[v] = lo; lo += sh_n[v]; sh_stream[v] = cu_share_stream(ctx, sh_lo[v], sh_n[v]); if (!sh_stream[v]) shares = false; }
                         if (lo > 32) shares = false;
                     }
                 }
             }
             if (g2g_opt(ctx, "WARN") && shares) {
                 fprintf(stderr, "[g2g] CU shares (units of 8 CUs, one per XCD):");
-                for (int v = 0; v < G2G_HDR; ++v) if (sh_n[v]) fprintf(stderr, " slot %d: %d..%d", v, sh_lo[v], sh_lo[v] + sh_n[v] - 1);
+                for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v]) fprintf(stderr, " slot %d: %d..%d", v, sh_lo[v], sh_lo[v] + sh_n[v] - 1);
                 fprintf(stderr, "\n");
             }
         }
@@ -1381,7 +1451,8 @@ extern "C" int g2g_batch_run(g2g_batch *b)
         const bool dbg = !dry && g2g_opt(ctx, "DEBUG") != 0;
         nlaunch = 0;
         auto launch_cus = [&](int slot) -> int { return shares ? 8 * sh_n[slot] : ncu; };
-        for (int v = 0; v < 4; ++v) {
+        for (int k2 = 0; k2 < 8; ++k2) {
+            const int v = k2 < 4 ? k2 : G2G_HDR + 2 + (k2 - 4);      // (variant slot; 4 .. 7: the bonus-aware instantiations)
             const int cnt = b->var_off[v + 1] - b->var_off[v];
             if (!cnt) continue;
             const int sk2 = nlaunch++ % G2G_NVS;
@@ -1405,9 +1476,9 @@ extern "C" int g2g_batch_run(g2g_batch *b)
                 if (!simscr2) { g2g_set_error("%s", "hipMalloc(column-score scratch)"); return G2G_ERR_NOMEM; }
             }
             if (dry) continue;
-            hipLaunchKernelGGL(v2k[v], dim3(grid), dim3(T2), b->lds2 + 4 * T2, vs2,
+            hipLaunchKernelGGL(v2k[k2], dim3(grid), dim3(T2), b->lds2 + 4 * T2, vs2,
                                (const DevProb *) b->d_probs, (const V2Tile *) (b->d_tiles + b->var_off[v]), cnt,
-                               b->d_flags + v, b->d_flags, b->gen, (int) b->lds2, b->v2_sweep ? (1 << 20) : b->v2_cols, pint2,
+                               qhead(v), b->d_flags, b->gen, (int) b->lds2, b->v2_sweep ? (1 << 20) : b->v2_cols, pint2,
                                (pro_off && pro_off + PRO_LDS_BYTES <= b->lds2) ? pro_off : 0, simscr2);
             HIPCHK(hipGetLastError());
             if (dbg) { hipError_t e3 = hipStreamSynchronize(vs2); fprintf(stderr, "[g2g] variant %d done: %s\n", v, hipGetErrorString(e3)); fflush(stderr); }
@@ -1494,26 +1565,27 @@ extern "C" int g2g_batch_run(g2g_batch *b)
             HIPCHK(hipEventRecord(ctx->vev[jev], vs));
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->vev[jev], 0));
         }
-        for (int v = 0; v < 4; ++v) {                        // v7: DPunit strips (no gap state, no LDS to speak of); v8: DPunit_nv strips
-            const int cnt = b->var_off[v + 17] - b->var_off[v + 16];
+        for (int v = 0; v < 6; ++v) {                        // v7: DPunit strips (no gap state, no LDS to speak of); v8: DPunit_nv strips; 4, 5: v7 with the bonus table
+            const int slot = v < 4 ? 16 + v : G2G_HDR + (v - 4);
+            const int cnt = b->var_off[slot + 1] - b->var_off[slot];
             if (!cnt) continue;
             typedef void (*v7k_t)(const DevProb *, const V2Tile *, int, int *, int *, int, int, double *);
-            static const v7k_t v7k[4] = {g2g_v7_ngp2, g2g_v7_ngp3, g2g_v8_ntv2, g2g_v8_ntv3};
+            static const v7k_t v7k[6] = {g2g_v7_ngp2, g2g_v7_ngp3, g2g_v8_ntv2, g2g_v8_ntv3, g2g_v7_ngp2_ib, g2g_v7_ngp3_ib};
             const int sk7 = nlaunch++ % G2G_NVS;
-            hipStream_t vs = launch_stream(v + 16, sk7);
-            const int ncu7 = launch_cus(v + 16);
+            hipStream_t vs = launch_stream(slot, sk7);
+            const int ncu7 = launch_cus(slot);
             if (!dry) HIPCHK(hipStreamWaitEvent(vs, ctx->vev[G2G_NVS], 0));
-            const int wpc = v < 2 ? 16 : 4;                  // (v8 holds its records' lengths in registers: one wave per SIMD)
+            const int wpc = (v < 2 || v >= 4) ? 16 : 4;      // (v8 holds its records' lengths in registers: one wave per SIMD)
             const int grid = std::min(cnt, ncu7 * wpc);
             const int pint = b->v2_sweep >= 2 ? b->v2_sweep : 4 * cnt <= ncu7 * wpc ? 4 : cnt < 4 * ncu7 * wpc ? 16 : 32;
-            double *simscr7 = sim_scratch(16 + v, grid);
+            double *simscr7 = sim_scratch(slot, grid);
             if (!simscr7) { g2g_set_error("%s", "hipMalloc(column-score scratch)"); return G2G_ERR_NOMEM; }
-            if (dbg) { fprintf(stderr, "[g2g] %s variant %d: %d strips, grid %d, publish every %d, gen %d\n", v < 2 ? "v7" : "v8", v & 1, cnt, grid, pint, b->gen); fflush(stderr); }
+            if (dbg) { fprintf(stderr, "[g2g] %s variant %d: %d strips, grid %d, publish every %d, gen %d\n", v < 2 ? "v7" : v < 4 ? "v8" : "v7 (bonus)", v & 1, cnt, grid, pint, b->gen); fflush(stderr); }
             if (dry) continue;
-            hipLaunchKernelGGL(v7k[v], dim3(grid), dim3(64), 0, vs, (const DevProb *) b->d_probs, (const V2Tile *) (b->d_tiles + b->var_off[v + 16]), cnt,
-                               b->d_flags + 16 + v, b->d_flags, b->gen, pint, simscr7);
+            hipLaunchKernelGGL(v7k[v], dim3(grid), dim3(64), 0, vs, (const DevProb *) b->d_probs, (const V2Tile *) (b->d_tiles + b->var_off[slot]), cnt,
+                               qhead(slot), b->d_flags, b->gen, pint, simscr7);
             HIPCHK(hipGetLastError());
-            if (dbg) { const auto t0 = std::chrono::steady_clock::now(); hipError_t e3 = hipStreamSynchronize(vs); fprintf(stderr, "[g2g] %s variant %d done: %s, %.1f ms\n", v < 2 ? "v7" : "v8", v & 1, hipGetErrorString(e3), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); fflush(stderr); }
+            if (dbg) { const auto t0 = std::chrono::steady_clock::now(); hipError_t e3 = hipStreamSynchronize(vs); fprintf(stderr, "[g2g] %s variant %d done: %s, %.1f ms\n", v < 2 ? "v7" : v < 4 ? "v8" : "v7 (bonus)", v & 1, hipGetErrorString(e3), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); fflush(stderr); }
             HIPCHK(hipEventRecord(ctx->vev[sk7], vs));
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->vev[sk7], 0));
         }
@@ -1644,6 +1716,7 @@ extern "C" int g2g_batch_run(g2g_batch *b)
                 if (!rc) for (size_t k = 0; k < lost.size(); ++k) {
                     free(b->recovered[lost[k]].trace);
                     b->recovered[lost[k]] = rr[k]; b->was_recovered[lost[k]] = 1;
+                    b->path_rec[lost[k]] = batch_path(rb, (int) k);
                 }
                 g2g_batch_free(rb);
             }
@@ -1686,6 +1759,16 @@ extern "C" int g2g_batch_fetch(g2g_batch *b, g2g_result *res)
         res[i].trace = (g2g_skl *) malloc(sizeof(g2g_skl) * nt);
         memcpy(res[i].trace, tmp + sizeof(double) + 2 * sizeof(int), sizeof(g2g_skl) * nt);
     }
+    return G2G_OK;
+}
+
+// Which kernel generation a problem runs on (after g2g_batch_prepare) / produced the result g2g_batch_fetch returns (after
+// g2g_batch_run: a DP re-run after a lost wait reports the kernel of its successful re-run).  1 g2g_forward_kernel, 2 the
+// 8-lanes-per-cell strips, 3 v3 / v3r, 6, 7, 8; 0 for a problem that was refused (g2g_result::status).
+extern "C" int g2g_batch_paths(const g2g_batch *b, int32_t *gen)
+{
+    if (!b || !gen) { g2g_set_error("g2g_batch_paths: %s", "bad argument"); return G2G_ERR_ARG; }
+    for (int i = 0; i < b->n; ++i) gen[i] = batch_path(b, i);
     return G2G_OK;
 }
 
@@ -1739,7 +1822,7 @@ extern "C" void g2g_batch_free(g2g_batch *b)
     release_arena(b);
     pool_give(b->ctx, b->d_tiles, b->tiles_cap);
     pool_give(b->ctx, b->d_flags, b->flags_cap);
-    for (int k = 0; k < 24; ++k) pool_give(b->ctx, b->simscr[k], b->simscr_cap[k]);
+    for (int k = 0; k < G2G_NVAR; ++k) pool_give(b->ctx, b->simscr[k], b->simscr_cap[k]);
     for (int k = 0; k < 6; ++k) pool_give(b->ctx, b->twin[k], b->twin_cap[k]);
     for (size_t i = 0; i < b->recovered.size(); ++i) free(b->recovered[i].trace);
     delete b;

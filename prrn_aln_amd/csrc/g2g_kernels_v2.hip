@@ -480,10 +480,13 @@ __device__ void v2_chain_left_staged(const DevProb &P, const V2Geom &G, LRec s0,
 struct CellSrc { LRec hd, hu, gu, g2u, hl, fl, f2l; };   // records the cell reads
 struct CellDst { LRec h, g, g2, f, f2; };                 // records it writes
 
-template <int KIND, bool NOLL3>
+// IB (the DP carries an intron-position bonus table, see v2_tile): on a table cell (bhit; team-uniform) H += bon_h and the
+// best non-diagonal record += bon_mx just before "diagonal wins ties" -- where g2g_forward_kernel's cell() does it
+// (fwd2c.h:446-453); the bonus stays in that record, as in the reference's *mx.
+template <int KIND, bool NOLL3, bool IB = false>
 __device__ void v2_cell(const DevProb &P, const V2Geom &G, const CellLists<LList16> &L_, int m, int n, int lane,
                         const CellSrc &S_, const CellDst &D_, bool do_vert, bool do_hori, uint8_t *tr,
-                        double dab, double pua, double pub
+                        double dab, double pua, double pub, const bool bhit, const double bon_h, const double bon_mx
 #ifdef G2G_V2_STAMP
                         , unsigned long long *stamp_acc, unsigned long long &stamp_t
 #endif
@@ -526,7 +529,7 @@ __device__ void v2_cell(const DevProb &P, const V2Geom &G, const CellLists<LList
     const double c_gnph2 = NOLL3 ? __shfl(r8, 6, TEAM) : 0;
     // ---- scalar decisions, replayed by every lane (fwd2c.h:395-453) ------------------------------
     double gop = (KIND == 2) ? c_d0 + c_d1 : c_d0;
-    const double hval = lval(S.hd) + (dab + gop);
+    double hval = lval(S.hd) + (dab + gop);
     const int hdir = isdiag(ldir(S.hd)) ? D_DIAG : D_NEWD;
     int bits = 0, win = 0;                          // win: 0 diag, 1 G, 2 G2, 3 F, 4 F2
     double mxval = NEVSEL;                          // mx = g: at the first row G is a black record
@@ -580,6 +583,14 @@ __device__ void v2_cell(const DevProb &P, const V2Geom &G, const CellLists<LList
             if (!f2_from_h) bits |= T_F2EXT;
             if (f2val >= mxval) { mxval = f2val; win = 4; }
         }
+    }
+    if (IB && bhit) {                                  // (win: the best non-diagonal record; the first row's black G absorbs its bonus)
+        hval += bon_h;
+        mxval += bon_mx;
+        if (win == 1) { if (do_vert) gval = mxval; }
+        else if (win == 2) g2val = mxval;
+        else if (win == 3) fval = mxval;
+        else f2val = mxval;
     }
     if (!(mxval > hval)) win = 0;                      // diagonal wins ties (fwd2c.h:453)
     if (!do_vert && win == 1) win = 0;                 // (the black G can never win)
@@ -669,7 +680,12 @@ __device__ __forceinline__ void list_g2l(li16 *gl, lf64 *fr, const DevSide &s, i
 //                            corner, hence the extra write-after-read dependency dep_war.
 //   cbH/cbF/cbF2[row]        each row's H corner and F records at the block's right edge
 //   colH[row]                the left boundary chain
-template <int KIND, bool NOLL3>
+// IB: DPs with an intron-position bonus table (DevProb::bon_*: cells row-major, n ascending within a row, all inside the
+// band; the per-row index sits behind bon_m's nbonus entries: first entry of row a.left + r at [nbonus + r], r = 0 .. rows).
+// The team of a row keeps a cursor into the row's entries and the column of the next one (the same three registers in each of
+// its 8 lanes): an ordinary cell pays one integer compare, a hit reads its two doubles from HBM.  No LDS.  The boundary chains
+// carry no bonus (initB, fwd2c.h:138-176, runs before the PfqItr pair exists, fwd2c.h:367-370).
+template <int KIND, bool NOLL3, bool IB = false>
 __device__ __forceinline__ void v2_tile(const DevProb &Pmem, lchar *lds, int ti, int tj, int nsteps, const int C,
                         const int *prog_up = 0, int *prog_self = 0, int *dbg = 0, const int pgen = 0, const int pint = 32,
                         const int *prog_left = 0, double *simscr = 0, int *failp = 0)
@@ -781,6 +797,18 @@ __device__ __forceinline__ void v2_tile(const DevProb &Pmem, lchar *lds, int ti,
     G2G_HB(prog_self, tid >> 6, 17)
     double sim_cur = 0, bc_cur = 0;
     bool have = false;
+    int ib_k = 0, ib_e = 0, ib_n = 0x7fffffff;                 // IB: cursor, end of the row's entries, column of the next one
+    const int *bon_n = 0;
+    const double *bon_h = 0, *bon_mx = 0;
+    if (IB) {
+        const int nbon = uni(Pmem.nbonus);
+        const int *brow = uni(Pmem.bon_m) + nbon;
+        bon_n = uni(Pmem.bon_n); bon_h = uni(Pmem.bon_h); bon_mx = uni(Pmem.bon_mx);
+        if (row_ok) { ib_k = brow[m - a.left]; ib_e = brow[m - a.left + 1]; }
+        if (ib_k < 0) ib_k = 0;
+        if (ib_e > nbon) ib_e = nbon;
+        if (ib_k < ib_e) ib_n = bon_n[ib_k];
+    }
     int rslot = (RC - team % RC) % RC;                     // ring slot of column cbase + s - team
     int wslot = 1 % RC;                                    // ring slot of column cbase + s + 1
     const bool stage_regs = G.ndw <= 64;                   // the records of the strip above are fetched a step ahead by the first wave, one dword per lane
@@ -929,7 +957,14 @@ __device__ __forceinline__ void v2_tile(const DevProb &Pmem, lchar *lds, int ti,
             G2G_HB(prog_self, tid >> 6, 6)
             const double pua = a.nils ? unpa(P, m, n) : pua_row;
             const double pub = bc_cur * a_efq * -P.u;                       // unp1(bsi, asi), maln.h:185-187
-            v2_cell<KIND, NOLL3>(P, G, L, m, n, lane, S, D, do_vert, do_hori, tr, sim_cur, pua, pub
+            bool bhit = false;
+            double bh = 0, bmx = 0;
+            if (IB && n == ib_n) {
+                bhit = true; bh = bon_h[ib_k]; bmx = bon_mx[ib_k];
+                ++ib_k;
+                ib_n = ib_k < ib_e ? bon_n[ib_k] : 0x7fffffff;
+            }
+            v2_cell<KIND, NOLL3, IB>(P, G, L, m, n, lane, S, D, do_vert, do_hori, tr, sim_cur, pua, pub, bhit, bh, bmx
 #ifdef G2G_V2_STAMP
                                  , stamp_acc, stamp_t
 #endif
@@ -1205,7 +1240,7 @@ __device__ unsigned long long g2g_wait_acc[4];
 // each thread adds (tid == 0) to the queue head, parks its result in LDS, and slot 0 is the tile.
 #define V2_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
 NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int lds_tile_off, int C, int sweep, int pro_off, double *simscr)
-#define V2_KERNEL(NAME, KIND, N3)                                                                   \
+#define V2_KERNEL(NAME, KIND, N3, IB)                                                               \
 V2_SIG(NAME, __launch_bounds__(G2G_V2_THREADS, G2G_V2_MINWAVES))                                    \
 {                                                                                                   \
     extern __shared__ __attribute__((aligned(16))) char g2g_lds[];                                  \
@@ -1236,7 +1271,7 @@ V2_SIG(NAME, __launch_bounds__(G2G_V2_THREADS, G2G_V2_MINWAVES))                
         }                                                                                           \
         __syncthreads();                                                                            \
         V2_WAIT_T1                                                                                  \
-        v2_tile<KIND, N3>(probs[T.prob], (lchar *) g2g_lds, T.ti, sweep ? 0 : T.tj, T.nsteps, C, pu, ps, done + G2G_HDR, gen, sweep, pl, \
+        v2_tile<KIND, N3, IB>(probs[T.prob], (lchar *) g2g_lds, T.ti, sweep ? 0 : T.tj, T.nsteps, C, pu, ps, done + G2G_HDR, gen, sweep, pl, \
                           (sweep && simscr) ? simscr + (size_t) blockIdx.x * G2G_SIMBLK_STRIDE : (double *) 0, failp); \
         V2_WAIT_T2                                                                                  \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                            \
@@ -1249,10 +1284,15 @@ V2_SIG(NAME, __launch_bounds__(G2G_V2_THREADS, G2G_V2_MINWAVES))                
     }                                                                                               \
 }
 #ifdef G2G_TU_V2
-V2_KERNEL(g2g_v2_hf2, 1, false)
-V2_KERNEL(g2g_v2_hf3, 1, true)
-V2_KERNEL(g2g_v2_pf2, 2, false)
-V2_KERNEL(g2g_v2_pf3, 2, true)
+V2_KERNEL(g2g_v2_hf2, 1, false, false)
+V2_KERNEL(g2g_v2_hf3, 1, true, false)
+V2_KERNEL(g2g_v2_pf2, 2, false, false)
+V2_KERNEL(g2g_v2_pf3, 2, true, false)
+V2_KERNEL(g2g_v2_hf2_ib, 1, false, true)                 // DPs with an intron-position bonus table
+V2_KERNEL(g2g_v2_hf3_ib, 1, true, true)
+V2_KERNEL(g2g_v2_pf2_ib, 2, false, true)
+V2_KERNEL(g2g_v2_pf3_ib, 2, true, true)
 #else
 V2_SIG(g2g_v2_hf2, ); V2_SIG(g2g_v2_hf3, ); V2_SIG(g2g_v2_pf2, ); V2_SIG(g2g_v2_pf3, );
+V2_SIG(g2g_v2_hf2_ib, ); V2_SIG(g2g_v2_hf3_ib, ); V2_SIG(g2g_v2_pf2_ib, ); V2_SIG(g2g_v2_pf3_ib, );
 #endif

@@ -57,7 +57,36 @@ __device__ __forceinline__ void v7_chain_tile(const DevProb &Pmem, const int whi
 }
 
 struct V7Strip : StripTraits { static constexpr bool REC_GLB = false; };      // (and no strip_where: no HW_ID for the stall report)
+// The intron-position bonus of forwardB (fwd2c.h:446-452) on a cell the decisions of which are made: H += bh, the best
+// non-diagonal record += bmx, THEN "diagonal wins ties" -- what g2g_forward_kernel's cell() does in place.  The best
+// non-diagonal record is found again from the four values, in v3_decide's order (G; G2 if greater; F, F2 if not smaller);
+// the bonus stays in that record (the row below / the next column read it), as it does in the reference's *mx.
+// (First row: mx is the black G, NEVSEL absorbs the bonus and nothing is stored.)
 template <bool NOLL3>
+__device__ __forceinline__ void strip_bonus(Dec &d, const bool do_vert, const bool do_hori, const double bh, const double bmx)
+{
+    int w = 1;
+    double mxv = NEVSEL;
+    if (do_vert) { mxv = d.gval; if (NOLL3 && d.g2val > mxv) { mxv = d.g2val; w = 2; } }
+    if (do_hori) {
+        if (d.fval >= mxv) { mxv = d.fval; w = 3; }
+        if (NOLL3 && d.f2val >= mxv) { mxv = d.f2val; w = 4; }
+    }
+    d.hval += bh;
+    mxv += bmx;
+    if (w == 1) { if (do_vert) d.gval = mxv; }
+    else if (w == 2) d.g2val = mxv;
+    else if (w == 3) d.fval = mxv;
+    else d.f2val = mxv;
+    d.win = (mxv > d.hval) ? w : 0;                      // diagonal wins ties (fwd2c.h:453)
+    if (!do_vert && w == 1) d.win = 0;
+}
+// IB: the DP carries a bonus table (DevProb::bon_*: cells row-major, n ascending within a row, all inside the band; behind
+// bon_m's nbonus entries sits the per-row index -- first entry of row a.left + r at [nbonus + r], r = 0 .. rows).  The lane
+// owns a row, so it keeps a cursor into the row's entries and the column of the next one: an ordinary cell pays one integer
+// compare, a hit reads its two doubles from HBM.  3 VGPRs, no LDS.  The boundary chains carry no bonus: initB (fwd2c.h:138-176)
+// never calls match_score, the PfqItr pair is made after it (fwd2c.h:367-370) -- v7_chain_tile serves both instantiations.
+template <bool NOLL3, bool IB = false>
 __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const int ti, const int nsteps,
                                          const int *prog_up, int *prog_self, int *dbg, const int pgen, const int pint, const int *prog_left,
                                          double *simscr, int *failp)
@@ -139,6 +168,18 @@ __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const 
     RS hu = rs_black(), gu = rs_black(), g2u = rs_black(), hd;
     const bool do_vert = m > a.left;
     const bool wr_rows = mend < a.right;                   // a strip below will read this strip's last row
+    int ib_k = 0, ib_e = 0, ib_n = 0x7fffffff;                 // IB: cursor, end of the row's entries, column of the next one
+    const GLB int *bon_n = 0;
+    const GLB double *bon_h = 0, *bon_mx = 0;
+    if (IB) {
+        const int nbon = uni(Pmem.nbonus);
+        const GLB int *brow = glb(uni(Pmem.bon_m)) + nbon;
+        bon_n = glb(uni(Pmem.bon_n)); bon_h = glb(uni(Pmem.bon_h)); bon_mx = glb(uni(Pmem.bon_mx));
+        if (row_ok) { ib_k = brow[m - a.left]; ib_e = brow[m - a.left + 1]; }
+        if (ib_k < 0) ib_k = 0;
+        if (ib_e > nbon) ib_e = nbon;
+        if (ib_k < ib_e) ib_n = bon_n[ib_k];
+    }
     team_sync();
     unsigned st_h = 0, st_g = 0, st_g2 = 0;
     bool st_prev = false;
@@ -198,7 +239,12 @@ __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const 
             c.d0 = 0; c.d1 = 0;
             c.gnpv = isvert(s_gu.dir) ? 0. : gv; c.gopv = isvert(s_hu.dir) ? 0. : gv; c.gnpv2 = isvert(s_g2u.dir) ? 0. : gv;
             c.gnph = ishori(s_fl.dir) ? 0. : gh; c.goph = ishori(s_hl.dir) ? 0. : gh; c.gnph2 = ishori(s_f2l.dir) ? 0. : gh;
-            const Dec d = v3_decide<1, NOLL3>(P, c, hd, s_hu, s_gu, s_g2u, s_hl, s_fl, s_f2l, do_vert, do_hori, sim_cur, pua, pub);
+            Dec d = v3_decide<1, NOLL3>(P, c, hd, s_hu, s_gu, s_g2u, s_hl, s_fl, s_f2l, do_vert, do_hori, sim_cur, pua, pub);
+            if (IB && n == ib_n) {
+                strip_bonus<NOLL3>(d, do_vert, do_hori, bon_h[ib_k], bon_mx[ib_k]);
+                ++ib_k;
+                ib_n = ib_k < ib_e ? bon_n[ib_k] : 0x7fffffff;
+            }
             int trb = 0;
             v3_outputs<0, NOLL3>(d, 0, 0, do_vert, do_hori, myH, myG, myG2, oF, oF2, trb);
             const int dd = m + n;
@@ -220,7 +266,7 @@ __device__ __forceinline__ void v7_strip(const DevProb &Pmem, lchar *lds, const 
 
 #define V7_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
 NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr)
-#define V7_KERNEL(NAME, N3)                                                                         \
+#define V7_KERNEL(NAME, N3, IB)                                                                       \
 V7_SIG(NAME, __launch_bounds__(64))                                                                 \
 {                                                                                                   \
     __shared__ __attribute__((aligned(16))) unsigned v7_lds[64 + 32];                               \
@@ -238,15 +284,17 @@ V7_SIG(NAME, __launch_bounds__(64))                                             
         if (strip_dp_dead(failp, s_vals)) { strip_release(done + T.self, strip_done_word(gen)); continue; } \
         const int *pl = T.dep_left >= 0 ? done + T.dep_left : (const int *) 0;                      \
         const int *pu = T.dep_up >= 0 ? done + T.dep_up : (const int *) 0;                          \
-        v7_strip<N3>(probs[T.prob], (lchar *) v7_lds, T.ti, T.nsteps, pu, done + T.self, done + G2G_HDR, gen, pint, pl, \
+        v7_strip<N3, IB>(probs[T.prob], (lchar *) v7_lds, T.ti, T.nsteps, pu, done + T.self, done + G2G_HDR, gen, pint, pl, \
                      simscr + (size_t) blockIdx.x * G2G_SIMBLK_STRIDE, failp);                             \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                            \
         __syncthreads();                                                                            \
     }                                                                                               \
 }
 #ifdef G2G_TU_V78
-V7_KERNEL(g2g_v7_ngp2, false)
-V7_KERNEL(g2g_v7_ngp3, true)
+V7_KERNEL(g2g_v7_ngp2, false, false)
+V7_KERNEL(g2g_v7_ngp3, true, false)
+V7_KERNEL(g2g_v7_ngp2_ib, false, true)                  // DPs with an intron-position bonus table
+V7_KERNEL(g2g_v7_ngp3_ib, true, true)
 #else
-V7_SIG(g2g_v7_ngp2, ); V7_SIG(g2g_v7_ngp3, );
+V7_SIG(g2g_v7_ngp2, ); V7_SIG(g2g_v7_ngp3, ); V7_SIG(g2g_v7_ngp2_ib, ); V7_SIG(g2g_v7_ngp3_ib, );
 #endif

@@ -142,11 +142,21 @@ class Batch:
     def arena_bytes(self) -> int:
         return lib().g2g_batch_arena_bytes(self._h)
 
+    def paths(self) -> List[int]:
+        """g2g_batch_paths: the kernel generation of every problem (1, 2, 3, 6, 7, 8; 0: refused) -- the one chosen, or after
+        run() the one that produced the fetched result"""
+        gen = (C.c_int32 * max(1, self.n))()
+        rc = lib().g2g_batch_paths(self._h, gen)
+        if rc:
+            raise G2GError("g2g_batch_paths rc=%d: %s" % (rc, last_error()))
+        return [int(gen[i]) for i in range(self.n)]
+
     def fetch(self):
         res = (_abi.Result * self.n)()
         rc = lib().g2g_batch_fetch(self._h, res)
         if rc:
             raise G2GError("g2g_batch_fetch rc=%d: %s" % (rc, last_error()))
+        self.last_rr = [(int(res[i].rr[0]), int(res[i].rr[1])) for i in range(self.n)]      # g2g_result::rr of the same call
         return Context._results(res, self.n)
 
     def spscore(self, sps, skls):
