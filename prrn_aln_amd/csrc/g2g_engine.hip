@@ -373,10 +373,12 @@ struct Blob {                       // host image of the input part of the arena
 extern "C" void g2g_batch_free(g2g_batch *b);
 // Variant slots (one queue, one persistent launch each).  [0, G2G_HDR): the kernels without a bonus table, their queue heads
 // are the first G2G_HDR words of d_flags (g2g_strip.h).  [G2G_HDR, G2G_NVAR): the bonus-aware instantiations -- g2g_v7_ngp{2,3}_ib
-// at 24 / 25, g2g_v2_{hf2,hf3,pf2,pf3}_ib at 26 .. 29 (odd slots: Noll 3, as below); their heads live at d_flags + xq_off.
-#define G2G_NVAR (G2G_HDR + 6)
+// at 24 / 25, g2g_v2_{hf2,hf3,pf2,pf3}_ib at 26 .. 29, g2g_v8_ntv{2,3}_ib at 30 / 31 (odd slots: Noll 3, as below); their heads
+// live at d_flags + xq_off.
+#define G2G_NVAR (G2G_HDR + 8)
 static inline bool slot_v7ib(int v) { return v >= G2G_HDR && v < G2G_HDR + 2; }
-static inline bool slot_v2ib(int v) { return v >= G2G_HDR + 2 && v < G2G_NVAR; }
+static inline bool slot_v2ib(int v) { return v >= G2G_HDR + 2 && v < G2G_HDR + 6; }
+static inline bool slot_v8ib(int v) { return v >= G2G_HDR + 6 && v < G2G_NVAR; }
 struct g2g_batch {
     g2g_ctx *ctx;
     int n;
@@ -422,7 +424,7 @@ struct g2g_batch {
     int hdr_img[G2G_HDR + G2G_HDRN];       // host image of the queue heads + wait header of the current run
     std::vector<const g2g_problem *> src;        // the caller's problems (kept alive by the caller until the batch is freed): a DP
                                                  // that lost a wait is re-run from here on the non-polling kernel
-    std::vector<char> ib;                        // per problem: runs on a bonus-aware strip kernel (g2g_v7_*_ib / g2g_v2_*_ib)
+    std::vector<char> ib;                        // per problem: runs on a bonus-aware strip kernel (g2g_v7_*_ib / g2g_v2_*_ib / g2g_v8_*_ib)
     std::vector<int> path_rec;                   // kernel generation of a recovered DP's successful re-run (g2g_batch_paths)
     int xq_off;                                  // offset in d_flags of the queue heads of the variant slots G2G_HDR .. G2G_NVAR - 1
     int fail_off;                                // offset of the per-DP fail flags in d_flags
@@ -949,13 +951,13 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
         }
         if (d.nbonus) {
             // The intron-position bonus: g2g_forward_kernel (v1), and the bonus-aware instantiations of the strips without gap
-            // state (v7) and of the 8-lanes-per-cell strips (v2, sweep mode) -- not v3 / v3r / v6 (register-bound) and not v8, so an
-            // annotated _hf / _pf DP goes to v2 whatever would otherwise have claimed it, within v2's own limits, and _nv stays
-            // on v1.  NO_STRIP_BONUS: v1 for all of them, as before the strips knew the bonus.
+            // state (v7), of the naive-record strips (v8) and of the 8-lanes-per-cell strips (v2, sweep mode) -- not v3 / v3r / v6
+            // (register-bound), so an annotated _hf / _pf DP goes to v2 whatever would otherwise have claimed it, within v2's own
+            // limits.  NO_STRIP_BONUS: v1 for all of them, as before the strips knew the bonus.
             const int was = d.v2_ok;
             d.v2_ok = 0;
             if (!g2g_opt(ctx, "NO_STRIP_BONUS")) {
-                if (was == 7) d.v2_ok = 7;
+                if (was == 7 || was == 8) d.v2_ok = was;
                 else if (was >= 1 && was <= 6 && (d.kind == 1 || d.kind == 2) && b->v2_sweep && std::max(p->a.len, p->b.len) < 32768 &&
                          v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, b->v2_threads) + 4 * b->v2_threads <= V2_LDS_MAX) d.v2_ok = 1;
             }
@@ -1072,7 +1074,7 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
             //  or a handful of balanced divisions would cost every strip of the sweep its occupancy)
             int v6cls = 0;
             if (d.v2_ok == 6) { const int tot = v6_layout(v6_rows_bytes(d), (d.capa + 3) & ~3, v6_ring_need(prob[i])).total; v6cls = (d.noll == 3 ? 1 : 0) + (tot > V6_SMALL_LDS ? 4 : tot > V6_CLASS_A ? 2 : 0); }
-            const int var = b->ib[i] ? (d.v2_ok == 7 ? G2G_HDR + (d.noll == 3 ? 1 : 0) : G2G_HDR + 2 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0)) : d.v2_ok == 8 ? 18 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 7 ? 16 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 6 ? v6_slot(v6cls) : (d.v2_ok - 1) * 4 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0);
+            const int var = b->ib[i] ? (d.v2_ok == 7 ? G2G_HDR + (d.noll == 3 ? 1 : 0) : d.v2_ok == 8 ? G2G_HDR + 6 + (d.noll == 3 ? 1 : 0) : G2G_HDR + 2 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0)) : d.v2_ok == 8 ? 18 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 7 ? 16 + (d.noll == 3 ? 1 : 0) : d.v2_ok == 6 ? v6_slot(v6cls) : (d.v2_ok - 1) * 4 + (d.kind == 2 ? 2 : 0) + (d.noll == 3 ? 1 : 0);
             b->var_cells[var] += b->cells[i];
             if (d.v2_ok == 6) {
                 v6rows[v6cls] = std::max(v6rows[v6cls], v6_rows_bytes(d));
@@ -1215,6 +1217,7 @@ static double variant_cost(int v)
     const double n3 = (v & 1) ? 1.4 : 1.0;                  // odd slots: Noll 3
     if (slot_v7ib(v)) return 0.8 * n3;                      // the bonus-aware instantiations: as their kernels
     if (slot_v2ib(v)) return (v < G2G_HDR + 4 ? 2.0 : 5.0) * n3;
+    if (slot_v8ib(v)) return 1.2 * n3;
     if (v < 2) return 2.0 * n3;                             // v2 _hf
     if (v < 4) return 5.0 * n3;                             // v2 _pf
     if (v < 8) return 2.5 * n3;                             // v3 with LDS lists
@@ -1327,6 +1330,7 @@ extern "C" int g2g_batch_run(g2g_batch *b)
             const int T2s = b->v2_threads;
             auto wpc_of = [&](int v) -> int {                 // resident workgroups per CU of variant slot v
                 if (slot_v7ib(v)) return 16;
+                if (slot_v8ib(v)) return 4;
                 if (v < 4 || slot_v2ib(v)) return std::max(1, std::min(2048 / T2s, (int) (V2_LDS_MAX / (b->lds2 + 4 * (size_t) T2s))));
                 if (v < 12) { const int t = b->v3lds[v - 4].total; return t > 0 ? std::max(1, std::min(16, (int) (V2_LDS_MAX / (size_t) t))) : 1; }
                 if (v < 16 || v >= 20) { const int cls = v < 16 ? v - 12 : v - 16; const int t = b->v6lds[cls].total; return t > 0 ? std::max(1, std::min(4, (int) (V2_LDS_MAX / (size_t) t))) : 1; }
@@ -1565,27 +1569,29 @@ extern "C" int g2g_batch_run(g2g_batch *b)
             HIPCHK(hipEventRecord(ctx->vev[jev], vs));
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->vev[jev], 0));
         }
-        for (int v = 0; v < 6; ++v) {                        // v7: DPunit strips (no gap state, no LDS to speak of); v8: DPunit_nv strips; 4, 5: v7 with the bonus table
-            const int slot = v < 4 ? 16 + v : G2G_HDR + (v - 4);
+        for (int v = 0; v < 8; ++v) {                        // v7: DPunit strips (no gap state, no LDS to speak of); v8: DPunit_nv strips; 4, 5 / 6, 7: v7 / v8 with the bonus table
+            const int slot = v < 4 ? 16 + v : v < 6 ? G2G_HDR + (v - 4) : G2G_HDR + 6 + (v - 6);
+            const bool is_v8 = (v >= 2 && v < 4) || v >= 6;
+            const char *const vname = v < 2 ? "v7" : v < 4 ? "v8" : v < 6 ? "v7 (bonus)" : "v8 (bonus)";
             const int cnt = b->var_off[slot + 1] - b->var_off[slot];
             if (!cnt) continue;
             typedef void (*v7k_t)(const DevProb *, const V2Tile *, int, int *, int *, int, int, double *);
-            static const v7k_t v7k[6] = {g2g_v7_ngp2, g2g_v7_ngp3, g2g_v8_ntv2, g2g_v8_ntv3, g2g_v7_ngp2_ib, g2g_v7_ngp3_ib};
+            static const v7k_t v7k[8] = {g2g_v7_ngp2, g2g_v7_ngp3, g2g_v8_ntv2, g2g_v8_ntv3, g2g_v7_ngp2_ib, g2g_v7_ngp3_ib, g2g_v8_ntv2_ib, g2g_v8_ntv3_ib};
             const int sk7 = nlaunch++ % G2G_NVS;
             hipStream_t vs = launch_stream(slot, sk7);
             const int ncu7 = launch_cus(slot);
             if (!dry) HIPCHK(hipStreamWaitEvent(vs, ctx->vev[G2G_NVS], 0));
-            const int wpc = (v < 2 || v >= 4) ? 16 : 4;      // (v8 holds its records' lengths in registers: one wave per SIMD)
+            const int wpc = is_v8 ? 4 : 16;                  // (v8 holds its records' lengths in registers: one wave per SIMD)
             const int grid = std::min(cnt, ncu7 * wpc);
             const int pint = b->v2_sweep >= 2 ? b->v2_sweep : 4 * cnt <= ncu7 * wpc ? 4 : cnt < 4 * ncu7 * wpc ? 16 : 32;
             double *simscr7 = sim_scratch(slot, grid);
             if (!simscr7) { g2g_set_error("%s", "hipMalloc(column-score scratch)"); return G2G_ERR_NOMEM; }
-            if (dbg) { fprintf(stderr, "[g2g] %s variant %d: %d strips, grid %d, publish every %d, gen %d\n", v < 2 ? "v7" : v < 4 ? "v8" : "v7 (bonus)", v & 1, cnt, grid, pint, b->gen); fflush(stderr); }
+            if (dbg) { fprintf(stderr, "[g2g] %s variant %d: %d strips, grid %d, publish every %d, gen %d\n", vname, v & 1, cnt, grid, pint, b->gen); fflush(stderr); }
             if (dry) continue;
             hipLaunchKernelGGL(v7k[v], dim3(grid), dim3(64), 0, vs, (const DevProb *) b->d_probs, (const V2Tile *) (b->d_tiles + b->var_off[slot]), cnt,
                                qhead(slot), b->d_flags, b->gen, pint, simscr7);
             HIPCHK(hipGetLastError());
-            if (dbg) { const auto t0 = std::chrono::steady_clock::now(); hipError_t e3 = hipStreamSynchronize(vs); fprintf(stderr, "[g2g] %s variant %d done: %s, %.1f ms\n", v < 2 ? "v7" : v < 4 ? "v8" : "v7 (bonus)", v & 1, hipGetErrorString(e3), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); fflush(stderr); }
+            if (dbg) { const auto t0 = std::chrono::steady_clock::now(); hipError_t e3 = hipStreamSynchronize(vs); fprintf(stderr, "[g2g] %s variant %d done: %s, %.1f ms\n", vname, v & 1, hipGetErrorString(e3), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); fflush(stderr); }
             HIPCHK(hipEventRecord(ctx->vev[sk7], vs));
             HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->vev[sk7], 0));
         }

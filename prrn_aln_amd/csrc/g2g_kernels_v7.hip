@@ -62,7 +62,10 @@ struct V7Strip : StripTraits { static constexpr bool REC_GLB = false; };      //
 // non-diagonal record is found again from the four values, in v3_decide's order (G; G2 if greater; F, F2 if not smaller);
 // the bonus stays in that record (the row below / the next column read it), as it does in the reference's *mx.
 // (First row: mx is the black G, NEVSEL absorbs the bonus and nothing is stored.)
-template <bool NOLL3>
+// SEL: the write-back as selects.  The four-way store chain of Noll 3 reaches the code generator as ONE store through a
+// computed offset, which keeps the whole Dec in scratch (g2g_v7_ngp3_ib: 80 B); v8, one wave per SIMD already, asks for the
+// selects.  The v7 instantiations keep the form they were measured with.
+template <bool NOLL3, bool SEL = false>
 __device__ __forceinline__ void strip_bonus(Dec &d, const bool do_vert, const bool do_hori, const double bh, const double bmx)
 {
     int w = 1;
@@ -74,7 +77,12 @@ __device__ __forceinline__ void strip_bonus(Dec &d, const bool do_vert, const bo
     }
     d.hval += bh;
     mxv += bmx;
-    if (w == 1) { if (do_vert) d.gval = mxv; }
+    if (SEL) {
+        d.gval = (w == 1 && do_vert) ? mxv : d.gval;
+        if (NOLL3) d.g2val = w == 2 ? mxv : d.g2val;
+        d.fval = w == 3 ? mxv : d.fval;
+        if (NOLL3) d.f2val = w == 4 ? mxv : d.f2val;
+    } else if (w == 1) { if (do_vert) d.gval = mxv; }
     else if (w == 2) d.g2val = mxv;
     else if (w == 3) d.fval = mxv;
     else d.f2val = mxv;

@@ -211,7 +211,10 @@ __device__ __forceinline__ void v8_chain_tile(const DevProb &Pmem, const int whi
 }
 
 #define V8_SLOT(kind_, col) ((kind_) == 0 ? SLOT_H(col) : (kind_) == 1 ? 3 + ((col) & 1) : 5 + ((col) & 1))
-template <bool NOLL3>
+// IB: the DP carries a bonus table; cursor and strip_bonus as in v7_strip (g2g_kernels_v7.hip).  The bonus moves values and the
+// winner only: the sources of G / F (d.g_from_h ...) are chosen before it (fwd2c.h:446-453), so their lengths are untouched, and
+// H's lengths follow the winner AFTER the bonus.  v8_chain_tile carries none (initB) and serves both instantiations.
+template <bool NOLL3, bool IB = false>
 __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const int ti, const int nsteps,
                                          const int *prog_up, int *prog_self, int *dbg, const int pgen, const int pint, const int *prog_left,
                                          double *simscr, int *failp)
@@ -307,6 +310,18 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
     NL lhu = nl_zero(), lgu = nl_zero(), lg2u = nl_zero(), lhd;
     const bool do_vert = m > a.left;
     const bool wr_rows = mend < a.right;                   // a strip below will read this strip's last row
+    int ib_k = 0, ib_e = 0, ib_n = 0x7fffffff;             // IB: cursor, end of the row's entries, column of the next one
+    const GLB int *bon_n = 0;
+    const GLB double *bon_h = 0, *bon_mx = 0;
+    if (IB) {
+        const int nbon = uni(Pmem.nbonus);
+        const GLB int *brow = glb(uni(Pmem.bon_m)) + nbon;
+        bon_n = glb(uni(Pmem.bon_n)); bon_h = glb(uni(Pmem.bon_h)); bon_mx = glb(uni(Pmem.bon_mx));
+        if (row_ok) { ib_k = brow[m - a.left]; ib_e = brow[m - a.left + 1]; }
+        if (ib_k < 0) ib_k = 0;
+        if (ib_e > nbon) ib_e = nbon;
+        if (ib_k < ib_e) ib_n = bon_n[ib_k];
+    }
     team_sync();
     unsigned st_h = 0, st_g = 0, st_g2 = 0;
     bool st_prev = false;
@@ -376,7 +391,12 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
             c.d0 = cd[0];
             c.gnpv = cv[0]; c.gopv = cv[1]; c.gnpv2 = cv[2];
             c.gnph = ch[0]; c.goph = ch[1]; c.gnph2 = ch[2];
-            const Dec d = v3_decide<1, NOLL3>(P, c, hd, s_hu, s_gu, s_g2u, s_hl, s_fl, s_f2l, do_vert, do_hori, sim_cur, pua, pub);
+            Dec d = v3_decide<1, NOLL3>(P, c, hd, s_hu, s_gu, s_g2u, s_hl, s_fl, s_f2l, do_vert, do_hori, sim_cur, pua, pub);
+            if (IB && n == ib_n) {                         // before everything that reads d.win
+                strip_bonus<NOLL3, true>(d, do_vert, do_hori, bon_h[ib_k], bon_mx[ib_k]);
+                ++ib_k;
+                ib_n = ib_k < ib_e ? bon_n[ib_k] : 0x7fffffff;
+            }
             int trb = 0;
             v3_outputs<0, NOLL3>(d, 0, 0, do_vert, do_hori, myH, myG, myG2, oF, oF2, trb);
             // the lengths follow their records (update: fwd2c.cc:114-128)
@@ -413,7 +433,7 @@ __device__ __forceinline__ void v8_strip(const DevProb &Pmem, lchar *lds, const 
 
 #define V8_SIG(NAME, ATTR) extern "C" __global__ void ATTR                                         \
 NAME(const DevProb *probs, const V2Tile *tiles, int ntiles, int *qhead, int *done, int gen, int pint, double *simscr)
-#define V8_KERNEL(NAME, N3)                                                                         \
+#define V8_KERNEL(NAME, N3, IB)                                                                      \
 V8_SIG(NAME, __launch_bounds__(64))                                                                 \
 {                                                                                                   \
     __shared__ __attribute__((aligned(16))) unsigned v8_lds[96 + 64];                               \
@@ -431,15 +451,17 @@ V8_SIG(NAME, __launch_bounds__(64))                                             
         if (strip_dp_dead(failp, s_vals)) { strip_release(done + T.self, strip_done_word(gen)); continue; } \
         const int *pl = T.dep_left >= 0 ? done + T.dep_left : (const int *) 0;                      \
         const int *pu = T.dep_up >= 0 ? done + T.dep_up : (const int *) 0;                          \
-        v8_strip<N3>(probs[T.prob], (lchar *) v8_lds, T.ti, T.nsteps, pu, done + T.self, done + G2G_HDR, gen, pint, pl, \
+        v8_strip<N3, IB>(probs[T.prob], (lchar *) v8_lds, T.ti, T.nsteps, pu, done + T.self, done + G2G_HDR, gen, pint, pl, \
                      simscr + (size_t) blockIdx.x * G2G_SIMBLK_STRIDE, failp);                             \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                            \
         __syncthreads();                                                                            \
     }                                                                                               \
 }
 #ifdef G2G_TU_V78
-V8_KERNEL(g2g_v8_ntv2, false)
-V8_KERNEL(g2g_v8_ntv3, true)
+V8_KERNEL(g2g_v8_ntv2, false, false)
+V8_KERNEL(g2g_v8_ntv3, true, false)
+V8_KERNEL(g2g_v8_ntv2_ib, false, true)                  // DPs with an intron-position bonus table
+V8_KERNEL(g2g_v8_ntv3_ib, true, true)
 #else
-V8_SIG(g2g_v8_ntv2, ); V8_SIG(g2g_v8_ntv3, );
+V8_SIG(g2g_v8_ntv2, ); V8_SIG(g2g_v8_ntv3, ); V8_SIG(g2g_v8_ntv2_ib, ); V8_SIG(g2g_v8_ntv3_ib, );
 #endif
