@@ -258,19 +258,22 @@ struct B6 { Ring6 rs, rt; int os, ot, lens, lent, lenr; double rhf; };
 // dla): newgap(b.s, dlb, a.t|a.r, dla).  RV: df is the r view = an optional head entry {glen 0, freq hf} followed by the t
 // entries with glen + 1 (hf = 0: no head; its term is then +0).  lmax: the wave's longest s list.  Slots behind the row's
 // list hold key 0xFFFF / freq 0: their terms are +0 as well, so validity needs no test.
-template <int N, int NE, bool SCAN, bool RV>
+// M: the slots this instance runs, a compile-time bucket at or above the wave's longest t list (V6_XMERGES picks it).  Nothing
+// here is guarded by that length: slots between it and M are "behind the list" in every lane and add the same +0 that a lane
+// whose own list is shorter than the wave's has always added.  (With the length as a run-time guard inside the unrolled loops
+// the compiler kept all N slots in the kk loop and selected each one twice more on a loop-invariant "d < TA" mask.)
+template <int M, int N, int NE, bool SCAN, bool RV>
 __device__ __forceinline__ double v6_xmerge(const DH<NE> &ha, const DH<NE> &hb, const unsigned (&dk)[N], const double (&dfq)[N], const double hf,
-                                            const int TA, const B6 &B, const int lmax, const LS6 &W)
+                                            const B6 &B, const int lmax, const LS6 &W)
 {
-    unsigned j[N], jh = 0;
-    double S[N], Sh = 0;
+    static_assert(M <= N, "bucket beyond the register lists");
+    unsigned j[M], jh = 0;
+    double S[M], Sh = 0;
     if (RV) jh = dh_stretch<NE, SCAN>(0xFFFFu, ha, W, W.ia);
     V6_UNROLL
-    for (int d = 0; d < N; ++d) {
-        if (d < TA) {
-            j[d] = dh_stretch<NE, SCAN>(dk[d] + (RV ? 0x10000u : 0u), ha, W, W.ia);
-            S[d] = 0;
-        }
+    for (int d = 0; d < M; ++d) {
+        j[d] = dh_stretch<NE, SCAN>(dk[d] + (RV ? 0x10000u : 0u), ha, W, W.ia);
+        S[d] = 0;
     }
     for (int kk = lmax - 1; kk >= 0; --kk) {
         const bool valid = kk < B.lens;
@@ -281,14 +284,12 @@ __device__ __forceinline__ double v6_xmerge(const DH<NE> &ha, const DH<NE> &hb, 
         const unsigned i = valid ? iv : 0u;
         if (RV) Sh = i >= jh ? e.f : Sh;
         V6_UNROLL
-        for (int d = 0; d < N; ++d)
-            if (d < TA) S[d] = i >= j[d] ? e.f : S[d];
+        for (int d = 0; d < M; ++d) S[d] = i >= j[d] ? e.f : S[d];
     }
     double g = 0;
     if (RV) g += Sh * hf;
     V6_UNROLL
-    for (int d = 0; d < N; ++d)
-        if (d < TA) g += S[d] * dfq[d];
+    for (int d = 0; d < M; ++d) g += S[d] * dfq[d];
     return g;
 }
 
@@ -385,10 +386,19 @@ __device__ __forceinline__ bool v6_cell_pf(const DevProb &P, const LS6 &W, const
     {
         int lmax = 0;
         while (__ballot(B.lens > lmax)) ++lmax;
-        c.d1 = v6_xmerge<N, NE, SCAN, false>(a_hd, b_hd, A.tk, A.tf, 0., TAt, B, lmax, W) * P.basic_gop;
-        c.gnph = v6_xmerge<N, NE, SCAN, true>(a_fl, b_fl, A.tk, A.tf, A.rhf, TAt, B, lmax, W) * P.basic_gop;
-        c.goph = v6_xmerge<N, NE, SCAN, true>(a_hl, b_hl, A.tk, A.tf, A.rhf, TAt, B, lmax, W) * P.basic_gop;
-        c.gnph2 = NOLL3 ? v6_xmerge<N, NE, SCAN, true>(a_f2, b_f2, A.tk, A.tf, A.rhf, TAt, B, lmax, W) * P.basic_gop : 0;
+        // the slots of the merges: the smallest of 4, 8, 12, N that holds the wave's longest t list -- one wave-uniform branch per
+        // cell (TAt is a ballot count of v6_strip), outside the kk loops.  The SCAN instance (lists of nine entries and more) runs
+        // all N slots: it never counts, and one form keeps its code small.
+#define V6_XMERGES(M) {                                                                                                          \
+        c.d1 = v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, false>(a_hd, b_hd, A.tk, A.tf, 0., B, lmax, W) * P.basic_gop;           \
+        c.gnph = v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, true>(a_fl, b_fl, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop;       \
+        c.goph = v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, true>(a_hl, b_hl, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop;       \
+        c.gnph2 = NOLL3 ? v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, true>(a_f2, b_f2, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop : 0; }
+        if (SCAN || (N > 12 && TAt > 12)) V6_XMERGES(N)
+        else if (N > 8 && TAt > 8) V6_XMERGES(12)
+        else if (TAt > 4) V6_XMERGES(8)
+        else V6_XMERGES(4)
+#undef V6_XMERGES
     }
 #endif
     V6_STAMP(3)
