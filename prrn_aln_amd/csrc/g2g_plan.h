@@ -1,0 +1,398 @@
+// g2g_plan.h -- the host-side decisions of a batch run as plain values: which variant slot is which kernel, how the CUs are
+// shared out, the list of persistent launches, and the text of a time-out report.  Plain C++17 without HIP types (it
+// compiles with g++: tests/host/plan_main.cc pins all of it without a GPU); g2g_engine.hip executes what is planned here.
+#ifndef G2G_PLAN_H
+#define G2G_PLAN_H
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+#define G2G_NVAR 32                 // variant slots
+#define G2G_PLAN_HDR 24             // G2G_HDR of g2g_strip.h (the engine asserts that they agree)
+#define G2G_NVS 8                   // launch streams of a context (HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default: bench.py asks for 8)
+static const size_t V2_LDS_MAX = 160 * 1024;
+
+// ---- (a) the variant table -----------------------------------------------------------------------------------------
+// A variant slot is one queue and one persistent launch.  The queue heads of slots [0, G2G_HDR) are the first G2G_HDR words
+// of d_flags (g2g_strip.h), those of the bonus-aware instantiations (_ib, [G2G_HDR, G2G_NVAR)) live at d_flags + xq_off.
+// The family's number is the kernel generation of DevProb::v2_ok and of g2g_batch_paths' tally.
+enum G2GFamily { G2G_NONE = 0, G2G_V2 = 1, G2G_V3_LDS = 2, G2G_V3R = 3, G2G_V6 = 6, G2G_V7 = 7, G2G_V8 = 8 };
+enum G2GRecord { G2G_REC_NONE = 0, G2G_REC_HF = 1, G2G_REC_PF = 2 };
+struct G2GVariant {
+    const char *name;               // the kernel
+    G2GFamily fam;
+    G2GRecord rec;
+    bool noll3, ib;
+    int cls;                        // v6: footprint class A / B / C = 0 / 1 / 2 (the kernel is the same, the LDS plan is the launch's)
+    double cost;                    // relative cost of a cell on this kernel for Noll 2 (what the CU shares are proportional to)
+};
+static const G2GVariant G2G_VARIANT[G2G_NVAR] = {
+    {"g2g_v2_hf2", G2G_V2, G2G_REC_HF, false, false, -1, 2.0},        {"g2g_v2_hf3", G2G_V2, G2G_REC_HF, true, false, -1, 2.0},
+    {"g2g_v2_pf2", G2G_V2, G2G_REC_PF, false, false, -1, 5.0},        {"g2g_v2_pf3", G2G_V2, G2G_REC_PF, true, false, -1, 5.0},
+    {"g2g_v3_hf2", G2G_V3_LDS, G2G_REC_HF, false, false, -1, 2.5},    {"g2g_v3_hf3", G2G_V3_LDS, G2G_REC_HF, true, false, -1, 2.5},
+    {"", G2G_NONE, G2G_REC_NONE, false, false, -1, 0},                {"", G2G_NONE, G2G_REC_NONE, false, false, -1, 0},       // (_pf strips with one lane per cell: v6)
+    {"g2g_v3r_hf2", G2G_V3R, G2G_REC_HF, false, false, -1, 1.0},      {"g2g_v3r_hf3", G2G_V3R, G2G_REC_HF, true, false, -1, 1.0},
+    {"", G2G_NONE, G2G_REC_NONE, false, false, -1, 0},                {"", G2G_NONE, G2G_REC_NONE, false, false, -1, 0},
+    {"g2g_v6_pf2", G2G_V6, G2G_REC_PF, false, false, 0, 2.7},         {"g2g_v6_pf3", G2G_V6, G2G_REC_PF, true, false, 0, 2.7},
+    {"g2g_v6_pf2", G2G_V6, G2G_REC_PF, false, false, 1, 2.7},         {"g2g_v6_pf3", G2G_V6, G2G_REC_PF, true, false, 1, 2.7},
+    {"g2g_v7_ngp2", G2G_V7, G2G_REC_NONE, false, false, -1, 0.8},     {"g2g_v7_ngp3", G2G_V7, G2G_REC_NONE, true, false, -1, 0.8},
+    {"g2g_v8_ntv2", G2G_V8, G2G_REC_NONE, false, false, -1, 1.2},     {"g2g_v8_ntv3", G2G_V8, G2G_REC_NONE, true, false, -1, 1.2},
+    {"g2g_v6_pf2", G2G_V6, G2G_REC_PF, false, false, 2, 2.7},         {"g2g_v6_pf3", G2G_V6, G2G_REC_PF, true, false, 2, 2.7},
+    {"", G2G_NONE, G2G_REC_NONE, false, false, -1, 0},                {"", G2G_NONE, G2G_REC_NONE, false, false, -1, 0},
+    {"g2g_v7_ngp2_ib", G2G_V7, G2G_REC_NONE, false, true, -1, 0.8},   {"g2g_v7_ngp3_ib", G2G_V7, G2G_REC_NONE, true, true, -1, 0.8},
+    {"g2g_v2_hf2_ib", G2G_V2, G2G_REC_HF, false, true, -1, 2.0},      {"g2g_v2_hf3_ib", G2G_V2, G2G_REC_HF, true, true, -1, 2.0},
+    {"g2g_v2_pf2_ib", G2G_V2, G2G_REC_PF, false, true, -1, 5.0},      {"g2g_v2_pf3_ib", G2G_V2, G2G_REC_PF, true, true, -1, 5.0},
+    {"g2g_v8_ntv2_ib", G2G_V8, G2G_REC_NONE, false, true, -1, 1.2},   {"g2g_v8_ntv3_ib", G2G_V8, G2G_REC_NONE, true, true, -1, 1.2},
+};
+// The order in which a run launches its non-empty slots: v2 and its _ib; v3 / v3r (the _hf launch goes before the _pf launches of
+// v6 on purpose: submitted behind them -- whose persistent workgroups hold the LDS of every CU until their queues are empty -- it
+// runs after them instead of beside them: 845 ms per bench sweep instead of 757); v6, the larger footprint first; v7, v8, their _ib.
+static const int G2G_LAUNCH_ORDER[] = {0, 1, 2, 3, 26, 27, 28, 29, 4, 5, 6, 7, 8, 9, 10, 11, 21, 20, 15, 14, 13, 12, 16, 17, 18, 19, 24, 25, 30, 31};
+static const int G2G_NLAUNCH_ORDER = (int) (sizeof G2G_LAUNCH_ORDER / sizeof G2G_LAUNCH_ORDER[0]);
+
+static inline double variant_cost(int slot) { return G2G_VARIANT[slot].cost * (G2G_VARIANT[slot].noll3 ? 1.4 : 1.0); }
+static inline bool variant_is_v3(int slot) { return G2G_VARIANT[slot].fam == G2G_V3_LDS || G2G_VARIANT[slot].fam == G2G_V3R; }
+// index of a slot within its family's per-batch arrays: v3 / v3r -> v3lds[8] and the builder's need[8] (also the number the v3
+// debug lines and ONLY_VAR speak of), v6 -> v6lds[6] / twin[6] (footprint class x 2 + Noll 3); -1 for the other families
+static inline int variant_v3_index(int slot) { return variant_is_v3(slot) ? (G2G_VARIANT[slot].fam == G2G_V3R ? 4 : 0) + (G2G_VARIANT[slot].noll3 ? 1 : 0) : -1; }
+static inline int variant_v6_index(int slot) { return G2G_VARIANT[slot].fam == G2G_V6 ? 2 * G2G_VARIANT[slot].cls + (G2G_VARIANT[slot].noll3 ? 1 : 0) : -1; }
+// The slot of a DP: its kernel generation (DevProb::v2_ok), DP kind (2: _pf records, else _hf where the family has both), Noll,
+// whether it carries a bonus table, and for v6 its footprint class; -1 where no kernel exists for the combination.
+static inline int variant_slot(int generation, int kind, int noll, bool ib, int v6cls)
+{
+    for (int s = 0; s < G2G_NVAR; ++s) {
+        const G2GVariant &r = G2G_VARIANT[s];
+        if (r.fam == G2G_NONE || (int) r.fam != generation || r.noll3 != (noll == 3) || r.ib != ib) continue;
+        if (r.fam == G2G_V6 ? r.cls != v6cls : (r.rec != G2G_REC_NONE && r.rec != (kind == 2 ? G2G_REC_PF : G2G_REC_HF))) continue;
+        return s;
+    }
+    return -1;
+}
+// g2g_batch_paths' number of a generation: 1 g2g_forward_kernel, 2 the 8-lanes-per-cell strips, 3 v3 / v3r, 6, 7, 8
+static inline int family_path(int generation) { return generation == G2G_NONE ? 1 : generation == G2G_V2 ? 2 : generation == G2G_V3_LDS || generation == G2G_V3R ? 3 : generation; }
+
+// ---- what a run knows about its batch ------------------------------------------------------------------------------
+struct LdsFacts { int total, svals, rows, black; };           // of a V3Lds / V6Lds plan
+struct RunFacts {
+    int cnt[G2G_NVAR];              // queue entries per slot
+    long long cells[G2G_NVAR];      // in-band cells per slot
+    int ncu;
+    size_t lds2, lds2p;
+    int v2_threads, v2_sweep, v3_sweep, v2_cols, v3_cols;
+    LdsFacts v3[8], v6[6];
+    int v2_wpc, v3_wpc, v6_wpc;     // options V2_WPC / V3_WPC / V6_WPC when in 1 .. 32, else 0
+    bool only_var_set; int only_var;                          // option ONLY_VAR (profiling aid)
+    bool no_simblk, no_prostage, parallel_hf;
+    size_t pro_lds_bytes;           // PRO_LDS_BYTES of g2g_kernels_v2.hip
+    size_t simblk_bytes;            // column-score scratch of one workgroup (G2G_SIMBLK_STRIDE doubles)
+};
+static inline int plan_pro_off(const RunFacts &f) { return f.no_prostage ? 0 : (int) ((f.lds2p + 15) & ~(size_t) 15); }
+static inline int clamp_wpc(size_t lds_total, int most) { return lds_total > 0 ? std::max(1, std::min(most, (int) (V2_LDS_MAX / lds_total))) : 1; }
+// resident workgroups per CU of a slot, as the CU shares see them (the *_WPC options size grids only)
+static inline int share_wpc(const RunFacts &f, int slot)
+{
+    switch (G2G_VARIANT[slot].fam) {
+    case G2G_V2: return std::max(1, std::min(2048 / f.v2_threads, (int) (V2_LDS_MAX / (f.lds2 + 4 * (size_t) f.v2_threads))));
+    case G2G_V3_LDS: case G2G_V3R: return clamp_wpc((size_t) f.v3[variant_v3_index(slot)].total, 16);
+    case G2G_V6: return clamp_wpc((size_t) f.v6[variant_v6_index(slot)].total, 4);
+    case G2G_V7: return 16;
+    case G2G_V8: return 4;
+    default: return 1;
+    }
+}
+
+// ---- (b) CU shares -------------------------------------------------------------------------------------------------
+// The chip is cut into 32 units of 8 CUs (one CU slot of every XCD); a launch gets a contiguous range of units in proportion
+// to its estimated work, capped by what its strips can occupy (see cu_share_stream in g2g_engine.hip).
+struct ShareIn {
+    int cnt[G2G_NVAR]; long long cells[G2G_NVAR]; int wpc[G2G_NVAR];      // per slot: queue entries, in-band cells, resident workgroups per CU
+    int ncu;
+    bool mode_set; int mode;        // option CU_SHARES: 0 / 1 / 2: never / for runs that fill the machine twice over / always
+    bool debug, no_share_gap;
+    size_t mstream_cap;             // MSTREAM_MAX
+    std::vector<std::pair<int, int> > alive;                  // (lo, n) of the CU-mask streams the context holds
+};
+struct ShareOut { bool shares; int lo[G2G_NVAR], n[G2G_NVAR]; };
+static inline void cu_share_plan(const ShareIn &in, ShareOut &out)
+{
+    int *sh_lo = out.lo, *sh_n = out.n;
+    bool &shares = out.shares;
+    shares = false;
+    double work[G2G_NVAR], tot = 0;
+    int need[G2G_NVAR], nl = 0;
+    double demand = 0;
+    bool has_v6 = false;
+    for (int v = 0; v < G2G_NVAR; ++v) {
+        const int cnt = in.cnt[v];
+        work[v] = cnt ? (double) std::max<long long>(in.cells[v], 1) * variant_cost(v) : 0;
+        need[v] = cnt ? std::min(32, std::max(1, (cnt + 8 * in.wpc[v] - 1) / (8 * in.wpc[v]))) : 0;   // units its tiles can occupy
+        sh_lo[v] = 0; sh_n[v] = 0;
+        if (cnt) { ++nl; tot += work[v]; demand += (double) cnt / in.wpc[v]; }
+        if (cnt > 0 && G2G_VARIANT[v].fam == G2G_V6) has_v6 = true;
+    }
+    // Default: shares when no v6 launch is in the run -- the regime of a window of g2g_refine and of a rank's share of a sharded
+    // sweep (_pf on v2 beside _hf on v3r: the two kernels slow each other down on a shared CU; 1/8 of the bench sweep 179 -> 140 ms,
+    // 1/4 266 -> 245 ms, a window of the 256 x 1024 refinement 107 -> 102 ms).  Not with v6 in the run: its class of the most
+    // balanced divisions is bound by its DPs' critical path, needs many CUs for a short time, and a static share leaves them idle
+    // afterwards (a full sweep 1563 ms instead of 760, half of one 734 instead of 437).  CU_SHARES=0 / 1 / 2: never /
+    // for runs that fill the machine twice over / always.
+    const bool autosh = !in.mode_set && !has_v6;
+    const bool want = in.mode_set ? in.mode != 0 : autosh;
+    const bool force = (in.mode_set && in.mode >= 2) || autosh;
+    // only a run that fills the machine more than twice over is partitioned, and only if every launch can have a unit
+    if (!(want && in.ncu == 256 && nl >= 2 && nl <= (int) in.mstream_cap && (force || demand >= 2.0 * in.ncu) && tot > 0 && !in.debug)) return;      // (256 CUs in 8 XCDs: the mask layout the shares are written for)
+    int left = 32;
+    double wleft = tot;
+    bool done[G2G_NVAR];
+    for (int v = 0; v < G2G_NVAR; ++v) done[v] = work[v] == 0;
+    // launches whose tiles cannot fill their proportional share take what they can fill; the rest is re-divided
+    for (int round = 0; round < G2G_NVAR; ++round) {
+        bool changed = false;
+        for (int v = 0; v < G2G_NVAR; ++v) {
+            if (done[v]) continue;
+            const double prop = wleft > 0 ? left * work[v] / wleft : 0;
+            if (need[v] <= prop) { sh_n[v] = need[v]; left -= need[v]; wleft -= work[v]; done[v] = true; changed = true; }
+        }
+        if (!changed) break;
+    }
+    int open_ = 0;
+    for (int v = 0; v < G2G_NVAR; ++v) if (!done[v]) ++open_;
+    if (left < open_) return;
+    int given = 0;
+    double frac[G2G_NVAR];
+    for (int v = 0; v < G2G_NVAR; ++v) {
+        frac[v] = -1;
+        if (done[v]) continue;
+        const double prop = left * work[v] / wleft;
+        sh_n[v] = std::max(1, (int) prop);
+        frac[v] = prop - (int) prop;
+        given += sh_n[v];
+    }
+    while (given < left) {                       // largest remainders first
+        int best = -1;
+        for (int v = 0; v < G2G_NVAR; ++v) if (frac[v] >= 0 && (best < 0 || frac[v] > frac[best])) best = v;
+        if (best < 0) break;
+        ++sh_n[best]; frac[best] = -0.5; ++given;
+    }
+    while (given > left) {                       // (the minimum of one unit each overdrew: take from the largest)
+        int big = -1;
+        for (int v = 0; v < G2G_NVAR; ++v) if (!done[v] && sh_n[v] > 1 && (big < 0 || sh_n[v] > sh_n[big])) big = v;
+        if (big < 0) break;
+        --sh_n[big]; --given;
+    }
+    if (given != left) return;
+    // two launches (the common case: _pf on v2 beside _hf on v3r): a split within one unit of one already in use is
+    // as good, and keeps the number of queues down
+    if (nl == 2) {
+        int v0 = -1, v1 = -1;
+        for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v]) { if (v0 < 0) v0 = v; else v1 = v; }
+        if (v0 >= 0 && v1 >= 0 && sh_n[v0] + sh_n[v1] == 32) {
+            // (once the context holds its fill of shares, the nearest one is taken whatever the distance: creating and
+            //  destroying queues while launches are resident makes the scheduler rebuild its run list, which the waiting
+            //  waves see as a pause of some 10 ms)
+            const int tol = in.alive.size() + 2 > in.mstream_cap ? 32 : 1;
+            int best = -1;
+            for (const auto &m : in.alive) {
+                if (m.first != 0 || m.second < 1 || m.second > 31 || abs(m.second - sh_n[v0]) > tol) continue;
+                bool partner = false;
+                for (const auto &q : in.alive) if (q.first == m.second && q.second == 32 - m.second) partner = true;
+                if (partner && (best < 0 || abs(m.second - sh_n[v0]) < abs(best - sh_n[v0]))) best = m.second;
+            }
+            if (best > 0) { sh_n[v0] = best; sh_n[v1] = 32 - best; }
+        }
+    }
+    // ONE UNIT OF 8 CUs STAYS EMPTY BETWEEN TWO SHARES (taken from the larger one).  Every stalled pipeline head of round 4
+    // (20 of 20 events) was held by one of the LAST 24 workgroups of the `_pf` launch's 600 resident
+    // ones -- the three workgroups on each CU of the share's last unit, next to the other launch's share; with the gap:
+    // 5 whole refinements (4360 windows) without an event against 0.6 events per run before, 0.5 % slower.
+    // NO_SHARE_GAP restores adjacent shares.
+    const int gap = (!in.no_share_gap && nl == 2) ? 1 : 0;
+    if (gap) { int vb = -1; for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v] && (vb < 0 || sh_n[v] > sh_n[vb])) vb = v; if (vb >= 0 && sh_n[vb] > 2) --sh_n[vb]; }
+    int lo = 0;
+    bool first = true;
+    for (int v = 0; v < G2G_NVAR; ++v) if (sh_n[v]) { if (!first) lo += gap; first = false; sh_lo[v] = lo; lo += sh_n[v]; }
+    shares = lo <= 32;
+}
+
+// ---- (c) the launches of a run -------------------------------------------------------------------------------------
+// Publish intervals (sweep mode: how many steps a strip runs between two publishes of its progress).  Three rules, each measured
+// for its kernels: they differ on purpose.
+// v2 (8 lanes per cell).  A DP's critical path is columns + strips x (rows of a strip + interval): 32 steps when the strips outnumber
+// the resident workgroups many times over (throughput bound, fewer fences), 8 / 4 when they do not (a window of g2g_refine: the batch
+// is as slow as its longest pipeline; measured on batches of 1-16 full-size DPs with tools/latency_probe.py: 4 beats 16 by 14 % at
+// 8 DPs, 2 gains nothing more), 16 for a rank's share of a sharded sweep (1/8 of the bench sweep: 180 ms against 195 with 32).
+static inline int publish_interval_v2(int sweep, int cnt, int resident)
+{
+    return !sweep ? 0 : sweep >= 2 ? sweep : cnt <= 2 * resident ? 4 : cnt <= 4 * resident ? 8 : cnt <= 16 * resident ? 16 : 32;
+}
+// v3 / v3r (_hf, one lane per cell): at most 8 strips per CU count as resident, and there is no step at 8.
+static inline int publish_interval_v3(int sweep, int cnt, int cus, int wpc)
+{
+    return !sweep ? 0 : sweep >= 2 ? sweep : cnt <= cus * std::min(wpc, 8) ? 4 : cnt < 4 * cus * std::min(wpc, 8) ? 16 : 32;
+}
+// v6 / v7 / v8 (sweep mode only): 4 while the strips fill at most a quarter of the resident slots.  V2_SWEEP >= 2 sets it.
+static inline int publish_interval_strip(int v2_sweep, int cnt, int cus, int wpc)
+{
+    return v2_sweep >= 2 ? v2_sweep : 4 * cnt <= cus * wpc ? 4 : cnt < 4 * cus * wpc ? 16 : 32;   // (a power of 2)
+}
+
+struct Launch {
+    int slot, cnt;
+    int k;                          // launch stream / join event of the run (unless the slot has a CU share: then its stream)
+    int cus;                        // CUs of its share, or all
+    int grid, block; size_t lds;
+    int cols, pint, pro_off;        // kernel arguments: columns of a tile (1 << 20: sweep mode), publish interval, staged chains' LDS offset
+    size_t scratch_bytes;           // column-score scratch (0: the kernel gets none)
+    int twin_dw; size_t twin_bytes; // v6: the twin image of the strips' dynamic lists
+    bool after_hf;                  // v6: starts when the _hf (v3 / v3r) launches are done
+};
+static inline std::vector<Launch> launch_plan(const RunFacts &f, const ShareOut &sh)
+{
+    std::vector<Launch> plan;
+    const int pro_off = plan_pro_off(f);
+    const int T2 = f.v2_threads;
+    for (int o = 0; o < G2G_NLAUNCH_ORDER; ++o) {
+        const int slot = G2G_LAUNCH_ORDER[o];
+        const G2GVariant &var = G2G_VARIANT[slot];
+        const int cnt = f.cnt[slot];
+        if (!cnt || var.fam == G2G_NONE) continue;
+        if (variant_is_v3(slot) && f.only_var_set && f.only_var != variant_v3_index(slot)) continue;
+        Launch l;
+        l.slot = slot; l.cnt = cnt;
+        l.k = (int) plan.size() % G2G_NVS;                    // every persistent launch of a run takes the next stream
+        l.cus = sh.shares ? 8 * sh.n[slot] : f.ncu;
+        l.block = 64; l.cols = 0; l.twin_dw = 0; l.twin_bytes = 0; l.after_hf = false;
+        bool scratch = true;
+        switch (var.fam) {
+        case G2G_V2: {
+            const int wpc = f.v2_wpc ? f.v2_wpc : 2048 / T2;  // workgroups per CU the grid provides (LDS decides how many are resident)
+            l.grid = std::min(cnt, l.cus * wpc);
+            l.block = T2; l.lds = f.lds2 + 4 * T2;
+            l.cols = f.v2_sweep ? (1 << 20) : f.v2_cols;
+            l.pint = publish_interval_v2(f.v2_sweep, cnt, l.cus * std::max(1, std::min(wpc, (int) (V2_LDS_MAX / (f.lds2 + 4 * (size_t) T2)))));
+            l.pro_off = (pro_off && pro_off + f.pro_lds_bytes <= f.lds2) ? pro_off : 0;
+            scratch = f.v2_sweep && !f.no_simblk;
+            break; }
+        case G2G_V3_LDS: case G2G_V3R: {
+            const LdsFacts &LO = f.v3[variant_v3_index(slot)];
+            const bool swp = var.rec == G2G_REC_HF && f.v3_sweep;      // the _hf variants run in sweep mode
+            const int wpc = f.v3_wpc ? f.v3_wpc : clamp_wpc((size_t) LO.total, 16);     // resident tiles per CU (LDS-bound)
+            l.grid = std::min(cnt, l.cus * wpc);
+            l.lds = (size_t) LO.total;
+            l.cols = swp ? (1 << 20) : f.v3_cols;
+            l.pint = publish_interval_v3(swp ? f.v3_sweep : 0, cnt, l.cus, wpc);
+            l.pro_off = (pro_off && pro_off + (int) f.pro_lds_bytes <= LO.svals) ? pro_off : 0;
+            scratch = swp && !f.no_simblk;
+            break; }
+        case G2G_V6: {
+            const LdsFacts &LO = f.v6[variant_v6_index(slot)];
+            // The _pf launches start when the _hf launches are done.  A sweep is bound by throughput -- its time is the SUM of what the
+            // launches take alone (_hf 133 ms + _pf 610 ms for the bench sweep; the two footprint classes of v6 together take what
+            // they take one after the other) -- and side by side the two kernel shapes leave each other wave slots they cannot use
+            // (v3r: two waves per SIMD, v6: a whole SIMD's registers): 769 -> 744 ms.  PARALLEL_HF=1: side by side as before.
+            l.after_hf = !f.parallel_hf;
+            const int wpc = f.v6_wpc ? f.v6_wpc : clamp_wpc((size_t) LO.total, 4);      // resident strips per CU (LDS-bound; the kernel takes a whole SIMD's registers: four at most)
+            l.grid = std::min(cnt, l.cus * wpc);
+            l.lds = (size_t) LO.total;
+            l.pint = publish_interval_strip(f.v2_sweep, cnt, l.cus, wpc);
+            l.pro_off = (pro_off && pro_off + (int) f.pro_lds_bytes <= LO.svals) ? pro_off : 0;
+            // the twin image of the strips' dynamic lists (what does not fit their inline parts in LDS): two dwords per dword of rows
+            l.twin_dw = 2 * (LO.black - LO.rows) / 4 + 64;
+            l.twin_bytes = (size_t) l.grid * l.twin_dw * sizeof(unsigned);
+            break; }
+        default: {                                            // v7: DPunit strips (no gap state, no LDS to speak of); v8: DPunit_nv strips
+            const int wpc = var.fam == G2G_V8 ? 4 : 16;       // (v8 holds its records' lengths in registers: one wave per SIMD)
+            l.grid = std::min(cnt, l.cus * wpc);
+            l.lds = 0;
+            l.pint = publish_interval_strip(f.v2_sweep, cnt, l.cus, wpc);
+            l.pro_off = 0;
+            break; }
+        }
+        l.scratch_bytes = scratch ? (size_t) l.grid * f.simblk_bytes : 0;
+        plan.push_back(l);
+    }
+    return plan;
+}
+
+// ---- (d) the report of a time-out ----------------------------------------------------------------------------------
+struct TimeoutView {
+    const int *x;                   // the wait header as read back: x[0] time-outs, x[1] first queue slot, x[4 ..] the first time-out's snapshot (g2g_wait_ge)
+    const int *dump;                // the dump area (2 + dump_words x dump_strips words), or 0 when there is none
+    int dump_words, dump_strips;
+    int gen, n, fail_off;
+    bool is_retry;
+    double rt_ticks_per_ms;
+    struct Lost { int i, kernel, rows, cols; };
+    std::vector<Lost> lost;
+};
+static inline std::string timeout_report_text(const TimeoutView &t)
+{
+    char buf[6144];
+    int o = 0;
+    auto add = [&](const char *fmt, ...) { va_list ap; va_start(ap, fmt); if (o < (int) sizeof buf - 1) { const int w = vsnprintf(buf + o, sizeof buf - o, fmt, ap); if (w > 0) o += w; } va_end(ap); if (o > (int) sizeof buf - 1) o = (int) sizeof buf - 1; };
+    const int *x = t.x;
+    int kinds[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (const auto &l : t.lost) if (l.kernel >= 0 && l.kernel < 10) ++kinds[l.kernel];
+    add("%d waits timed out (first: queue slot %d, gen %d, batch of %d DPs): re-running %zu DP(s) %s; by kernel (0 v1, 1 v2, 2 v3, 3 v3r, 6 v6, 7 v7, 8 v8):",
+        x[0], x[1], t.gen, t.n, t.lost.size(), t.is_retry ? "on g2g_forward_kernel" : "(first on the ordinary kernels)");
+    for (int k = 0; k < 10; ++k) if (kinds[k]) add(" %d x kernel %d", kinds[k], k);
+    add("; the first:");
+    for (size_t k = 0; k < t.lost.size() && k < 6; ++k) add(" %d(kernel %d, %d x %d)", t.lost[k].i, t.lost[k].kernel, t.lost[k].rows, t.lost[k].cols);
+    add(". First time-out: DP %d, wanted gen %d col %d of word %d, saw gen %d col %d; the words at and below it (gen:col):",
+        x[7] - t.fail_off, (x[4] >> 20) & 0x7FF, x[4] & 0xFFFFF, x[6], (x[5] >> 20) & 0x7FF, x[5] & 0xFFFFF);
+    for (int k = 0; k < 8; ++k) add(" %d:%d", (x[8 + k] >> 20) & 0x7FF, x[8 + k] & 0xFFFFF);
+    if (!(x[16] == 0x7fffffff || (x[16] == 0 && x[17] == 0))) add("; producer's heartbeat: step %d place %d, 50 us later step %d place %d", x[16], x[17], x[18], x[19]);
+    add("; producer HW_ID %08x XCC %d, waiter HW_ID %08x XCC %d; waiters per XCC:", x[20], x[21] & 15, x[22], x[23] & 15);
+    for (int k = 0; k < 8; ++k) add(" %d", x[24 + k] / 64);
+    add("; their producers per XCC:");
+    for (int k = 0; k < 8; ++k) add(" %d", x[32 + k] / 64);
+    add("; by RMW %d:%d, loaded again %d:%d", (x[46] >> 20) & 0x7FF, x[46] & 0xFFFFF, (x[47] >> 20) & 0x7FF, x[47] & 0xFFFFF);
+    add("; columns the producer's waves left at their last publish (v2 / v3 strips): %d %d %d %d", x[42], x[43], x[44], x[45]);
+    {   // -DG2G_HEARTBEAT builds: (step, place) of up to four waves of a v2 / v3 producer, twice, 50 us apart (all zero otherwise)
+        bool any = false;
+        for (int k = 48; k < 64; ++k) if (x[k]) any = true;
+        if (any) {
+            add("; producer's waves (step:place, then 50 us later):");
+            for (int w = 0; w < 4; ++w) add(" w%d %d:%d -> %d:%d", w, x[48 + 2 * w], x[49 + 2 * w], x[56 + 2 * w], x[57 + 2 * w]);
+        }
+    }
+    add("; the blocker (lowest strip of this DP without a publish in this generation, %d below the polled one): word %d:%d, HW_ID %08x XCC %08x, taken-by marker %08x (gen %d, workgroup %d), past the left chain %08x, past its first look at the strip above %08x, first wave's last publish %d (markers carry the generation; 7fffffff: never written)",
+        x[64], (x[65] >> 20) & 0x7FF, x[65] & 0xFFFFF, x[66], x[67], x[68], (x[68] >> 20) & 0x7FF, x[68] & 0xFFFF, x[69], x[70], x[71]);
+    if (t.dump && t.dump[0] > 0) {
+        // the whole pipeline of the first time-out's DP as that waiter saw it: strips ti-1, ti-2, ... (word, HW_ID, markers, the
+        // two waves' last publish).  A strip is TIGHT when its predecessor is less than 48 columns ahead (it can only be waiting
+        // for it); the HEADS are the unfinished strips that are not tight: they wait for nobody's progress.
+        const int *dump = t.dump;
+        const int nd = std::min(dump[0], t.dump_strips), ti = dump[1];
+        const int g1 = x[4] & ~0xFFFFF;
+        auto colof = [&](int w) { return w < (g1 | 0) ? -1 : (w & 0xFFFFF); };      // -1: nothing in this generation
+        int heads = 0, unfinished = 0, untaken = 0;
+        add("; pipeline of that DP (%d strips above the waiter dumped): heads", nd);
+        for (int k = 0; k < nd; ++k) {
+            const int *d = dump + 2 + t.dump_words * k;
+            const int c = colof(d[0]);
+            if (c == 0xFFFFF) continue;
+            ++unfinished;
+            const bool taken = (d[2] & ~0xFFFFF) == (g1 | 0) || ((d[2] >> 20) & 0x7FF) == ((g1 >> 20) & 0x7FF);
+            if (!taken) ++untaken;
+            const int cp = k + 1 < nd ? colof(dump[2 + t.dump_words * (k + 1)]) : 0xFFFFF;      // predecessor (the top chain counts as finished)
+            if (cp == 0xFFFFF || cp - c >= 48) {
+                if (heads < 6) add(" [strip %d: col %d, predecessor %s%d, HW_ID %08x, taken %08x, past left chain %08x, past first look %08x, waves' last publish %d %d, waves' step:place %d:%d %d:%d]",
+                                   ti - 1 - k, c, cp == 0xFFFFF ? "finished " : "col ", cp == 0xFFFFF ? 0 : cp, d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10]);
+                ++heads;
+            }
+        }
+        add(" -- %d head(s), %d unfinished strip(s), %d of them not taken from the queue in this generation", heads, unfinished, untaken);
+    }
+    add("; chain words of this DP as the first waiter saw them (valid when the polled word is a strip's): left %d:%d, top %d:%d", (x[80] >> 20) & 0x7FF, x[80] & 0xFFFFF, (x[81] >> 20) & 0x7FF, x[81] & 0xFFFFF);
+    if (x[72]) add("; of the waves released when their DP was given up, the one with the lowest strip index (%d) was waiting on word %d for %d:%d and had last seen %d:%d (read-modify-write on release: %d:%d) after %d polls, %.0f ms of its own running time",
+                   0x7fffffff - x[72], x[75], (x[73] >> 20) & 0x7FF, x[73] & 0xFFFFF, (x[74] >> 20) & 0x7FF, x[74] & 0xFFFFF, (x[78] >> 20) & 0x7FF, x[78] & 0xFFFFF, x[76], x[77] * 65536. / t.rt_ticks_per_ms);
+    add("; waiting waves off the machine for > 4 ms at a stretch in this run: %d (longest %.1f ms)", x[40], x[41] * 1024. / t.rt_ticks_per_ms);
+    buf[o] = 0;
+    return buf;
+}
+#endif
