@@ -3,7 +3,10 @@
 // nuc2cvec / profile_p / profile_n / profile, src/mseq.cc:392-587) and the three views of the static gap profile (Gfq::Gfq /
 // seq2gfq, src/gfreq.cc:134-312) -- for a whole batch of groups at once.  Included by g2g_engine.hip (shares the context's stream,
 // staging buffer and device-memory pool).  The host formulation of the same arrays (g2g_host.cpp: mkthick, convseq, GfqBuilder)
-// is pinned on the reference's dumps; this one is pinned on the host's (tests/test_gpu_builders.py: every array bit for bit).
+// is pinned on the reference's dumps; this one is pinned on the host's (tests/test_gpu_builders.py: every array bit for bit, and
+// the twins of g2g_side::dev as the sign that the device built them).  tests/test_gpu_wide.py holds both to the reference at this
+// file's edges: 64 classes alive at a column (built here) and 65 (refused), 257 .. 4096 members (codes read in place, `pre` false)
+// and 4097 (refused).
 //
 // Mapping.  Everything that is a sum over the members of ONE column is independent of every other column: one THREAD per column
 // adds its members in member order (the order is the contract: sums are floating point).  That covers the thickness rows, the

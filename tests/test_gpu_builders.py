@@ -49,6 +49,22 @@ def same_problem(q, r, what):
                 assert np.array_equal(f1, f2), (what, side, "freq", v, np.flatnonzero(f1 != f2)[:8])
 
 
+def meant_for_device(side):
+    """what g2g_pwdm_create_batch hands to g2g_device_derive for certain: a group with gaps (its thickness rows and gap profile
+    are still to build) and without nil codes (no discounted terminal gaps: tgapf >= 1 or no terminal gap; the tests set no free
+    ends).  Gap-free groups go along only when they need vectors."""
+    return bool(side.dels) and not side.nils
+
+
+def check_twins(g, h, what):
+    """the device-built PwdM g carries device twins (g2g_side::dev) on every side the device is meant to build -- a refusal
+    that silently sent the call to the host builders would pass every array comparison --, the host-built h on none"""
+    for side in ("a", "b"):
+        s = getattr(g.problem, side)
+        assert s.dev or not meant_for_device(s), (what, side)
+        assert not getattr(h.problem, side).dev, (what, side)
+
+
 def test_device_builders_equal_host_builders_on_the_goldens(ctx):
     """every reference golden's pair of groups, built on the device in ONE batch per parameter set"""
     sets = {}
@@ -57,7 +73,7 @@ def test_device_builders_equal_host_builders_on_the_goldens(ctx):
         alp = params_from_golden(d)
         key = (alp.molc, alp.ls, alp.tgapf, alp.sh, alp.banded, alp.u, alp.v, alp.u1, alp.k1, alp.scale, alp.max_code, alp.simmtx.tobytes())
         sets.setdefault(key, []).append((os.path.basename(path), alp, d))
-    taken = 0
+    taken = gapped = 0
     for key, items in sets.items():
         alp = items[0][1]
         host, pairs = [], []
@@ -70,8 +86,11 @@ def test_device_builders_equal_host_builders_on_the_goldens(ctx):
             same_problem(g.problem, h.problem, name)
             sh, sg = op.spparams(h), op.spparams(g)
             assert (sh.vab, sh.basic_gep, sh.diffu, sh.diff_u) == (sg.vab, sg.basic_gep, sg.diffu, sg.diff_u), name
+            check_twins(g, h, name)
+            gapped += sum(1 for s in (g.problem.a, g.problem.b) if s.dev and s.dels)
         if alp.tgapf >= 1:
             taken += len(items)
+    assert gapped >= 40                  # sides with gaps that the device did build
     assert taken >= 40                   # (the tgapf < 1 goldens go through the host inside the same call)
 
 
@@ -91,6 +110,8 @@ def test_device_builders_on_whole_sweeps(ctx, case):
     for k, (h, g) in enumerate(zip(host.pwds, dev.pwds)):
         assert g.swp == h.swp
         same_problem(g.problem, h.problem, (case, k))
+        check_twins(g, h, (case, k))
+    assert sum(1 for g in dev.pwds for s in (g.problem.a, g.problem.b) if s.dev and s.dels) > 50
     pick = list(host.order[:: max(1, len(host) // 24)])
     rh = op.align2_batch(ctx, [host.pwds[k] for k in pick])
     rg = op.align2_batch(ctx, [dev.pwds[k] for k in pick])
@@ -108,3 +129,5 @@ def test_no_device_build_option_and_counters(ctx):
     b = sweep.Sweep(fam, alp, weighted=True, ctx=ctx)
     for h, g in zip(a.pwds, b.pwds):
         same_problem(g.problem, h.problem, "option")
+        check_twins(g, h, "option")      # NO_DEVICE_BUILD: no side carries twins; without it every side meant for the device does
+    assert any(s.dev and s.dels for g in b.pwds for s in (g.problem.a, g.problem.b))

@@ -17,41 +17,18 @@ import pytest
 
 import oraclelib
 from prrn_aln_amd import engine, operator as op
+from widelib import base as _base, list_lengths, member as _member, stair as group_a
 
 pytestmark = pytest.mark.gpu
 
-AA = "ACDEFGHIKLMNPQRSTVWY"
 LEN_A, LEN_B = 150, 140
 SLOTS = {2: 16, 3: 10}                          # G2G_V6_NA / G2G_V6_NA3: register slots of a row list (terminator included)
 FIRST, LAST, ACROSS = 60, 140, 65               # c0: long lists in strip 0 / in the partial strip of rows 128-149 / t list K - 1 in row 63, K in row 64
 
 
-def _base(seed, n):
-    rng = np.random.default_rng(seed)
-    return "".join(AA[i] for i in rng.integers(20, size=n))
-
-
-def _member(rng, base, gap_end=0, gap_len=0):
-    r = [AA[rng.integers(20)] if rng.random() < 0.2 else c for c in base]
-    for i in range(gap_end - gap_len, gap_end):
-        r[i] = "-"
-    return "".join(r)
-
-
-def group_a(K, c0, base, plain=2):
-    """`plain` members without a gap, then K members with gap runs of 1 .. K columns that end just before column c0"""
-    rng = np.random.default_rng(100 + K)
-    return [_member(rng, base) for _ in range(plain)] + [_member(rng, base, c0, g) for g in range(1, K + 1)]
-
-
 def group_b(base):
     rng = np.random.default_rng(7)
     return [_member(rng, base, e, g) for e, g in ((0, 0), (50, 2), (50, 3), (100, 4))]
-
-
-def list_lengths(side):
-    """entries (terminator not counted) of the s, t, r lists of rows -1 .. len - 1: [view][row + 1]"""
-    return [np.diff(np.ctypeslib.as_array(side.gfq.off[v], shape=(side.len + 2,))) - 1 for v in range(3)]
 
 
 class Case:

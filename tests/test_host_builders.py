@@ -11,6 +11,11 @@ import pytest
 from prrn_aln_amd import _abi, operator as op
 
 GOLD = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
+WIDE = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "wide", "*.npz")))   # tests/widelib.py: long gap lists, > 256 members
+
+
+def gold_id(p):
+    return ("wide/" if os.path.basename(os.path.dirname(p)) == "wide" else "") + os.path.basename(p)[:-4]
 
 
 def params_from_golden(d):
@@ -42,7 +47,7 @@ def arr(ptr, n, dtype):
     return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype).copy()
 
 
-@pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
+@pytest.mark.parametrize("path", GOLD + WIDE, ids=[gold_id(p) for p in GOLD + WIDE])
 def test_builders_match_reference(path):
     d = dict(np.load(path))
     alp = params_from_golden(d)

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 
 import oraclelib
+import widelib
 from prrn_aln_amd import _abi
+from test_host_builders import WIDE, gold_id
 
 GOLD = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
 
@@ -25,7 +27,14 @@ def test_goldens_present():
     assert nolls == {2, 3}
 
 
-@pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
+def test_wide_goldens_present():
+    """tests/golden/wide holds every case of widelib.names(), and each still has the list lengths and member counts it was made
+    for (hetero 62 .. 191, more than 256 members)"""
+    for name, d in widelib.load():
+        widelib.check_fixture(name, d)
+
+
+@pytest.mark.parametrize("path", GOLD + WIDE, ids=[gold_id(p) for p in GOLD + WIDE])
 def test_oracle_matches_reference(L, path):
     d = dict(np.load(path))
     h = _abi.problem_from_arrays(d)
@@ -59,7 +68,7 @@ def sp_from_golden(d):
                          float(d["diff_u"][0]))
 
 
-@pytest.mark.parametrize("path", SP_GOLD, ids=[os.path.basename(p)[:-4] for p in SP_GOLD])
+@pytest.mark.parametrize("path", SP_GOLD + WIDE, ids=[gold_id(p) for p in SP_GOLD + WIDE])
 def test_oracle_spscore(L, path):
     """f1: SpScore::calcSkl + rescale along the reference's own skeleton == the reference's Gsinfo.fstat (bit-exact)."""
     d = dict(np.load(path))

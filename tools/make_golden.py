@@ -22,10 +22,11 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 SAMPLE = "/root/reference/sample"
 
 
-def save(name, d):
+def save(name, d, sub=""):
     # drop bulky arrays nobody checks (nres is not read by the DP)
     d = {k: v for k, v in d.items() if not k.endswith("_nres")}
-    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **d)
+    os.makedirs(os.path.join(GOLD, sub), exist_ok=True)
+    np.savez_compressed(os.path.join(GOLD, sub, name + ".npz"), **d)
     print("%-28s mode %2d sim %3d Noll %d a %dx%d b %dx%d scr %.6f ntrace %d" % (
         name, d["alnmode"][0], d["sim2_kind"][0], d["Noll"][0], d["a_many"][0], d["a_len"][0],
         d["b_many"][0], d["b_len"][0], d["scr"][0] if "scr" in d else float("nan"),
@@ -254,13 +255,38 @@ def job_rect_dna_ls3():
     _rect_cases(R, "dna12x150_ls3", dict(n_seq=12, length=150, seed=48, alphabet=DNA, indel=0.03, max_indel=40), [0, 4, -1])
 
 
-JOBS = {"rect_protein": job_rect_protein, "rect_ls3": job_rect_ls3, "rect_dna_ls3": job_rect_dna_ls3, "intron": job_intron, "sim23": job_sim23, "protein": job_protein, "dna_ls3": job_dna_ls3, "protein_ls3": job_protein_ls3,
+def job_wide(ls=None):
+    """wide, gap-rich groups made by hand (tests/widelib.py): static and dynamic gap lists on both sides of every length the
+    engine changes path at, and groups of more than 256 members -> tests/golden/wide/ (a directory of its own: the globs over
+    tests/golden/*.npz keep their meaning).  One process per Noll."""
+    if ls is None:
+        for v in ("0", "3"):
+            subprocess.check_call([sys.executable, os.path.abspath(__file__), "wide", v])
+        return
+    import refdump
+    import widelib
+    R = refdump.RefLib(molc=refdump.PROTEIN, ls=ls)
+    for name in widelib.names():
+        if ("_noll3" in name) != (ls == 3):
+            continue
+        case = widelib.case_of(name)
+        ra, rb = widelib.rows(case)
+        wa, wb = widelib.weights(case) if name.endswith("_w") else (None, None)
+        ga = R.group(["a%d" % i for i in range(len(ra))], ra, wa)
+        gb = R.group(["b%d" % i for i in range(len(rb))], rb, wb)
+        d = R.align_dump(ga, gb)
+        widelib.check_fixture(name, d)                      # a case that lost its edge is not saved
+        save(name, d, "wide")
+        R.free(ga); R.free(gb)
+
+
+JOBS = {"wide": job_wide, "rect_protein": job_rect_protein, "rect_ls3": job_rect_ls3, "rect_dna_ls3": job_rect_dna_ls3, "intron": job_intron, "sim23": job_sim23, "protein": job_protein, "dna_ls3": job_dna_ls3, "protein_ls3": job_protein_ls3,
         "protein_tgapf": job_protein_tgapf, "w21_protein": job_w21_protein, "w21_dna_ls3": job_w21_dna_ls3}
 
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     if len(sys.argv) > 1:
-        JOBS[sys.argv[1]]()
+        JOBS[sys.argv[1]](*[int(v) for v in sys.argv[2:]])
     else:
         for j in JOBS:
             subprocess.check_call([sys.executable, os.path.abspath(__file__), j])
