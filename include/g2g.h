@@ -334,8 +334,8 @@ int        g2g_align2_batch(g2g_ctx *ctx, int n, g2g_pwdm *const *p, double *scr
  * WINDOW of upcoming divisions run as one batch on the GPU (speculation: the divisions behind an accepted move are drawn again).
  *   codes: len x many residue codes [column][member] (gap = 1), no all-gap column.
  *   tree : Ktree::lead[] (src/phyl.h): node id = tid, leaves 0 .. many-1 are the members, left / right / parent = -1 where
- *          absent, vol / cur = the Kirchhoff weights the reference's Ktree computed (building the tree is phylogeny code,
- *          outside this path).
+ *          absent, vol / cur = the Kirchhoff weights of Ktree::calcpw.  g2g_ktree_from_msa (below) builds it from the MSA
+ *          itself -- the reference's tree, bit for bit; a tree from elsewhere is taken as it is.
  *   opts : seed (Randiv's rn: 1 = "seed from rand()" as prrn does), maxitr (prrn -I, default 10), window (largest speculative
  *          batch, default 32).  rank / world / exchange: with world > 1 every rank calls g2g_refine with the SAME inputs; a
  *          window is sharded (largest rectangles first, round-robin), each rank scores its share and `exchange` all-gathers
@@ -384,6 +384,33 @@ typedef struct g2g_refine_stats {
 int        g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len, const uint8_t *codes, const g2g_tree *tree,
                       const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len, g2g_refine_step **steps, int *nsteps,
                       g2g_refine_stats *stats);
+
+/* ---- the weighting tree of an MSA ----------------------------------------------------------------------------------
+ * <-> Ssrel::calcweight (reference src/prrn5.cc:385-386): Ktree(msd) -- calcdistseq / pairdvn (src/phyl.cc:344-385,
+ * src/divseq.cc:33-63: the divergence of every pair of members over the columns of the alignment), DistTree::upg_method
+ * (src/phyl.cc:911-1026, UPGMA) and Knode::teachparent (:583-595) -- followed by Ktree::calcpw -> pairwt (:704-767, 813-826: the
+ * Kirchhoff weights vol / cur).  The divergences are computed on the GPU (csrc/g2g_ktree.hip: one launch for all pairs), the
+ * tree and the weights on the host; topology, heights and weights are the reference's, bit for bit.
+ *   codes  : len x many residue codes [column][member] as for g2g_refine; a code <= 1 is a gap (nil 0 counts as one: IsGap).
+ *   dist   : many (many - 1) / 2 doubles, pair (i < j) at j (j - 1) / 2 + i (the reference's elem()): 1 - mch / (0.8 gap + 0.2 unp +
+ *            mch + mmc) in the reference's operation order; a pair without any column gives what IEEE gives (NaN).
+ *   counts : 4 int32 per pair (matched, mismatched, unpaired columns, gaps opened), same order; may be NULL.
+ * Limits: 2 <= many <= 4096, len >= 1 (else G2G_ERR_ARG).  (Entry points added without a change of g2g_abi_version.) */
+typedef struct g2g_ktree {          /* all arrays malloc'ed, n_nodes = 2 * many - 1 long; release with g2g_ktree_free              */
+    int32_t n_nodes, root;          /* root: the node made last (n_nodes - 1)                                                    */
+    int32_t *left, *right, *parent, *ndesc;   /* -1 where absent; ndesc = leaves below the node (1 for a leaf)                   */
+    double  *height, *length, *res, *vol, *cur;   /* Knode::height (half the merge distance), ::length (branch to the parent),
+                                       ::res (resistance of the subtree), and the Kirchhoff weights                             */
+} g2g_ktree;
+int        g2g_msa_divergence(g2g_ctx *ctx, int many, int len, const uint8_t *codes, double *dist, int32_t *counts);
+/* The tree of a distance matrix in that layout: host only, needs no context; dist is not modified.  with_weights = 0 is the
+   Ktree(&dm) of the progressive start (src/prrn5.cc:978-979): topology, heights, lengths and res only, vol / cur are zero.
+   A NaN or negative distance: G2G_ERR_ARG, g2g_last_error names the pair.  left / right / parent / vol / cur are directly
+   usable as a g2g_tree. */
+int        g2g_ktree_from_dist(int many, const double *dist, int with_weights, g2g_ktree *out);
+/* = g2g_msa_divergence + g2g_ktree_from_dist(with_weights = 1) */
+int        g2g_ktree_from_msa(g2g_ctx *ctx, int many, int len, const uint8_t *codes, g2g_ktree *out);
+void       g2g_ktree_free(g2g_ktree *t);
 
 /* <-> VTYPE Ssrel::pairsum_ss(mSeq* sd, bool use_pw) (reference src/fspscore.cc:896-922; Sptree::sptree :784-821): the weighted
  * sum-of-pairs score of a whole MSA, the number prrn reports for an alignment (initial / refined, the -O4 line).  The reference

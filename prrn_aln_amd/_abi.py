@@ -77,6 +77,13 @@ class Tree(C.Structure):
                 ("parent", C.POINTER(C.c_int32)), ("vol", c_f64p), ("cur", c_f64p)]
 
 
+class KTreeOut(C.Structure):
+    """g2g_ktree: the tree g2g_ktree_from_dist / g2g_ktree_from_msa build (arrays owned by the library: g2g_ktree_free)"""
+    _fields_ = [("n_nodes", C.c_int32), ("root", C.c_int32), ("left", C.POINTER(C.c_int32)), ("right", C.POINTER(C.c_int32)),
+                ("parent", C.POINTER(C.c_int32)), ("ndesc", C.POINTER(C.c_int32)), ("height", c_f64p), ("length", c_f64p),
+                ("res", c_f64p), ("vol", c_f64p), ("cur", c_f64p)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32))
 
 

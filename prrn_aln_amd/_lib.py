@@ -80,6 +80,11 @@ def lib():
                              C.POINTER(C.POINTER(_abi.RefineStep)), C.POINTER(C.c_int), C.POINTER(_abi.RefineStats)]
     L.g2g_pairsum.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_int, C.c_int, _abi.c_u8p, C.POINTER(_abi.Tree), C.c_int,
                               C.POINTER(C.c_double)]
+    L.g2g_msa_divergence.argtypes = [C.c_void_p, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(C.c_int32)]
+    L.g2g_ktree_from_dist.argtypes = [C.c_int, _abi.c_f64p, C.c_int, C.POINTER(_abi.KTreeOut)]
+    L.g2g_ktree_from_msa.argtypes = [C.c_void_p, C.c_int, C.c_int, _abi.c_u8p, C.POINTER(_abi.KTreeOut)]
+    L.g2g_ktree_free.restype = None
+    L.g2g_ktree_free.argtypes = [C.POINTER(_abi.KTreeOut)]
     bind_level1(L)
     _lib = L
     return L

@@ -61,6 +61,25 @@ def alnscored_batch(ctx, prm: "_abi.Params", seqs: Sequence[np.ndarray], ia: Seq
     return out, st
 
 
+def msa_divergence(ctx, codes: np.ndarray):
+    """g2g_msa_divergence: the divergence of every pair of members of an MSA ((len, many) uint8 codes, <= 1 = gap) as the
+    reference's calcdistseq / pairdvn computes it (src/phyl.cc:344-385, src/divseq.cc:33-63) -- the distances its weighting tree
+    is built from.  Returns (dist float64[npairs], counts int32[npairs, 4] = matched, mismatched, unpaired, gaps); pair (i < j)
+    is entry j (j - 1) / 2 + i."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    if codes.ndim != 2:
+        raise ValueError("codes must be (len, many)")
+    ln, many = codes.shape
+    npairs = max(many * (many - 1) // 2, 0)
+    dist = np.zeros(npairs, np.float64)
+    counts = np.zeros((npairs, 4), np.int32)
+    rc = lib().g2g_msa_divergence(ctx._h, many, ln, codes.ctypes.data_as(_abi.c_u8p), dist.ctypes.data_as(_abi.c_f64p),
+                                  counts.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise G2GError("g2g_msa_divergence rc=%d: %s" % (rc, last_error()))
+    return dist, counts
+
+
 def alignb_ng_batch(ctx, prm: "_abi.Params", seqs: Sequence[np.ndarray], ia: Sequence[int], ib: Sequence[int]):
     """alignB_ng for every index pair: [(score, skeleton (n, 2) int32, status)]"""
     L = lib()

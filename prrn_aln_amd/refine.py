@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 
@@ -18,16 +18,58 @@ from ._lib import G2GError, last_error, lib
 @dataclass
 class KTree:
     """The weighting tree as the reference's Ktree::lead[] holds it: node id = tid (leaves 0..n-1 = members), -1 where a link is
-    absent, vol / cur = the Kirchhoff weights the reference computed (building the tree is phylogeny code, outside this path)."""
+    absent, vol / cur = the Kirchhoff weights of Ktree::calcpw.  from_msa / from_dist build it in the library (g2g_ktree_from_msa /
+    g2g_ktree_from_dist: the reference's tree, bit for bit) and fill height / length / res / ndesc / root as well; a tree from
+    elsewhere is given by its first five arrays."""
     left: List[int]
     right: List[int]
     parent: List[int]
     vol: List[float]
     cur: List[float]
+    height: Optional[List[float]] = None
+    length: Optional[List[float]] = None
+    res: Optional[List[float]] = None
+    ndesc: Optional[List[int]] = None
+    root: Optional[int] = None
 
     @property
     def n_leaves(self) -> int:
         return (len(self.left) + 1) // 2
+
+    @classmethod
+    def _take(cls, T: "_abi.KTreeOut") -> "KTree":
+        """copy a g2g_ktree out of the library's arrays and release them"""
+        n = T.n_nodes
+        get = lambda p: np.ctypeslib.as_array(p, shape=(n,)).tolist()
+        t = cls(get(T.left), get(T.right), get(T.parent), get(T.vol), get(T.cur), get(T.height), get(T.length), get(T.res),
+                get(T.ndesc), int(T.root))
+        lib().g2g_ktree_free(C.byref(T))
+        return t
+
+    @classmethod
+    def from_dist(cls, dist, with_weights: bool = True) -> "KTree":
+        """g2g_ktree_from_dist: UPGMA tree (DistTree::upg_method) of a condensed distance vector -- pair (i < j) at j (j - 1) / 2 + i --
+        and, with_weights, the Kirchhoff weights (Ktree::calcpw); host only.  Without them vol / cur are zero."""
+        d = np.ascontiguousarray(dist, np.float64).reshape(-1)
+        many = int(round((1 + (1 + 8 * len(d)) ** 0.5) / 2))
+        if many * (many - 1) // 2 != len(d):
+            raise ValueError("%d distances are not the pairs of a whole number of members" % len(d))
+        T = _abi.KTreeOut()
+        rc = lib().g2g_ktree_from_dist(many, d.ctypes.data_as(_abi.c_f64p), 1 if with_weights else 0, C.byref(T))
+        if rc != 0:
+            raise G2GError("g2g_ktree_from_dist rc=%d: %s" % (rc, last_error()))
+        return cls._take(T)
+
+    @classmethod
+    def from_msa(cls, ctx, codes: np.ndarray) -> "KTree":
+        """g2g_ktree_from_msa: the weighting tree of an MSA ((len, many) uint8 codes), divergences on the GPU"""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        ln, many = codes.shape
+        T = _abi.KTreeOut()
+        rc = lib().g2g_ktree_from_msa(ctx._h, many, ln, codes.ctypes.data_as(_abi.c_u8p), C.byref(T))
+        if rc != 0:
+            raise G2GError("g2g_ktree_from_msa rc=%d: %s" % (rc, last_error()))
+        return cls._take(T)
 
     def to_c(self):
         """(g2g_tree, arrays to keep alive)"""
