@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libg2g.so")
 HDR = [os.path.join(os.path.dirname(HERE), "include", "g2g.h"), os.path.join(CSRC, "g2g_device.h"), os.path.join(CSRC, "g2g_internal.h"),
-       os.path.join(CSRC, "g2g_strip.h")]
+       os.path.join(CSRC, "g2g_strip.h"), os.path.join(CSRC, "g2g_lds.h")]
 
 _K1, _K2, _K3 = "g2g_kernels.hip", "g2g_kernels_v2.hip", "g2g_kernels_v3.hip"
 # unit -> (source, files it includes besides the headers)

@@ -468,59 +468,13 @@ static V3Lds v3_layout(int rows_bytes, int ca4max, int apool, int bpool, int C)
     L.total = o;
     return L;
 }
-// LDS plan of the v6 kernel (g2g_kernels_v6.hip): ring rows of dynamic lists, black lists, staging scalars, the ring of
-// b's static lists (3 views x rs entries x 16 B), queue scratch, sinks
-struct V6Ring { int rs[3]; };                  // ring entries per view; entries of the t lists of the strip that has the most
-static V6Lds v6_layout(int rows_bytes, int ca4max, const V6Ring &R)
-{
-    V6Lds L;
-    int o = 0;
-    auto take = [&](int bytes) { int r = o; o = (o + bytes + 15) & ~15; return r; };
-    L.rows = take(rows_bytes);
-    L.black = take(4 * (ca4max + 8));
-    L.stsc = take(4 * 28);
-    for (int v = 0; v < 3; ++v) { L.rs[v] = R.rs[v]; L.ringf[v] = take(8 * R.rs[v]); }
-    for (int v = 0; v < 3; ++v) L.ringk[v] = take(v < 2 ? 4 * R.rs[v] : 0);       // (view 2: an array of head freqs per column, no keys)
-    L.svals = take(4 * 64);
-    L.sink = take(4 * 64 + 16 * 64);
-    L.total = o;
-    return L;
-}
-// A launch has ONE LDS plan, the largest of its DPs, and LDS decides how many strips a CU holds (the kernel takes a whole SIMD's
-// registers: four per CU at most).  Since the dynamic lists keep only their inline parts in LDS (g2g_kernels_v6.hip, LS6) a strip
-// of the bench sweep takes 26-30 KB; class A (up to 40 KB, four strips per CU) holds all of those.  The balanced divisions whose
-// column lists need a 1024-entry ring (40-53 KB: three strips per CU) are FASTER on v2 (8 lanes per cell, 16-row strips): the
-// bench sweep 714 -> 660 ms with them there (same box; limit 46 KB 709, 49 KB 738, 36 KB 663, 30 KB 694), so the default limit
-// of v6 is class A's.  Classes B (up to V6_SMALL_KB) and C (V6_LARGE_KB) stay as options for measurements.
-static const int V6_CLASS_A = 40 * 1024;
+// LDS plan of the v6 kernel: V6Ring, v6_ring_need, v6_layout, v6_rows_bytes and the footprint class A live in g2g_plan.h
 static int v6_small_lds(const g2g_ctx *c) { const char *e = g2g_opt(c, "V6_SMALL_KB"); return e ? atoi(e) * 1024 : 40 * 1024; }
 #define V6_SMALL_LDS (v6_small_lds(ctx))
 static int v6_large_lds(const g2g_ctx *c) { const char *e = g2g_opt(c, "V6_LARGE_KB"); return e ? atoi(e) * 1024 : 0; }
 #define V6_LARGE_LDS (v6_large_lds(ctx))
-static int v6_rows_bytes(const DevProb &d)
-{
-    const int lsz = v6_inline_dw((d.capa + 3) & ~3) + v6_inline_dw((d.capb + 3) & ~3);      // the INLINE parts of a record's two lists (LS6)
-    return 65 * v3_pitch(d.noll == 3 ? 9 : 6, lsz) * 4 + 32;
-}
-// ring entries the v6 kernel needs per view for this problem: the most list entries (terminators not counted) any window
-// of V6_WINDOW consecutive columns of b holds (a ring is indexed by compact pool position & (rs - 1))
-static V6Ring v6_ring_need(const g2g_problem *p)
-{
-    V6Ring R;
-    const int lo = p->b.left, hi = p->b.right;
-    for (int v = 0; v < 3; ++v) {
-        const int32_t *off = p->b.gfq.off[v];
-        int need = 1;
-        for (int c = lo; c < hi; ++c) {
-            const int e = std::min(c + V6_WINDOW, hi);
-            need = std::max(need, (off[e + 1] - (e + 1)) - (off[c + 1] - (c + 1)));
-        }
-        int rs = 32;
-        while (rs < need) rs <<= 1;
-        R.rs[v] = v < 2 ? rs : V6_RHCOLS;                    // (the r view is derived from the t ring: only its head freqs, one per column)
-    }
-    return R;
-}
+static int v6_rows_bytes(const DevProb &d) { return v6_rows_bytes(d.capa, d.capb, d.noll); }
+static V6Ring v6_ring_need(const g2g_problem *p) { return v6_ring_need(p->b.gfq.off, p->b.left, p->b.right); }
 struct V3Need { int rows_bytes, ca4, apool, bpool, total; };
 static V3Need v3_need(const DevProb &d, const g2g_problem *p, int C, bool areg = false)
 {
@@ -797,7 +751,8 @@ static int build_queues(g2g_ctx *ctx, g2g_batch *b, const g2g_problem *const *pr
     std::vector<int> ip;                              // the other DPs: chains in the prologue kernel
     const bool chainq = !g2g_opt(ctx, "NO_CHAINQ");
     int v6rows[6] = {0, 0, 0, 0, 0, 0}, v6ca4[6] = {0, 0, 0, 0, 0, 0};
-    V6Ring v6rs[6] = {{{32, 32, 32}}, {{32, 32, 32}}, {{32, 32, 32}}, {{32, 32, 32}}, {{32, 32, 32}}, {{32, 32, 32}}};
+    V6Ring v6rs[6];
+    for (int v = 0; v < 6; ++v) { const V6Ring r0 = {{32, 32, V6_RHCOLS}, 4, {1, 1, 1}}; v6rs[v] = r0; }
     V3Need need[8];
     memset(need, 0, sizeof need);
     for (int i = 0; i < n; ++i) {
@@ -828,7 +783,7 @@ static int build_queues(g2g_ctx *ctx, g2g_batch *b, const g2g_problem *const *pr
             const int v6cls = variant_v6_index(var);
             v6rows[v6cls] = std::max(v6rows[v6cls], v6_rows_bytes(d));
             v6ca4[v6cls] = std::max(v6ca4[v6cls], (d.capa + 3) & ~3);
-            { const V6Ring rn = v6_ring_need(prob[i]); for (int q = 0; q < 3; ++q) v6rs[v6cls].rs[q] = std::max(v6rs[v6cls].rs[q], rn.rs[q]); }
+            v6_ring_max(v6rs[v6cls], v6_ring_need(prob[i]));
         } else if (d.v2_ok >= 7) {
         } else if (d.v2_ok >= 2) {
             const V3Need nd = v3_need(d, prob[i], C, d.v2_ok == 3);
@@ -882,6 +837,18 @@ static int build_queues(g2g_ctx *ctx, g2g_batch *b, const g2g_problem *const *pr
     }
     b->var_off[G2G_NVAR] = (int) all.size();
     for (int v = 0; v < 6; ++v) b->v6lds[v] = v6_layout(v6rows[v], v6ca4[v], v6rs[v]);
+    {   // what the v6 launches of this batch were given, read back as option V6_RING_PLAN (g2g_get_option): per launch that has
+        // strips "<class x 2 + Noll 3>:<S of the s ring>,<S of the t ring>,<T>,<LDS bytes>", joined by ';' (empty: no v6 launch)
+        std::string plan;
+        for (int s = 0; s < G2G_NVAR; ++s) {
+            const int v = variant_v6_index(s);
+            if (v < 0 || b->var_off[s + 1] == b->var_off[s]) continue;
+            char buf[96];
+            snprintf(buf, sizeof buf, "%s%d:%d,%d,%d,%d", plan.empty() ? "" : ";", v, b->v6lds[v].rs[0], b->v6lds[v].rs[1], b->v6lds[v].rtail, b->v6lds[v].total);
+            plan += buf;
+        }
+        ctx->opt["V6_RING_PLAN"] = std::make_pair(true, plan);
+    }
     for (int v = 0; v < 8; ++v) b->v3lds[v] = v3_layout(need[v].rows_bytes, need[v].ca4, need[v].apool, need[v].bpool, b->v3_cols);
     // test hook: G2G_INJECT_STALL=<i> makes the first strip / tile of problem i depend on a flag nobody ever writes
     if (const char *e = g2g_opt(ctx, "INJECT_STALL")) {
@@ -1408,7 +1375,7 @@ static int launch_variant(g2g_ctx *ctx, g2g_batch *b, const Launch &l, hipStream
     case G2G_V6: {
         const V6Lds &LO = batch_v6lds(b, slot);
         const int v = variant_v6_index(slot);
-        if (dbg) { fprintf(stderr, "[g2g] v6 variant %d: %d strips, grid %d, lds %d (rings %d / %d / %d entries), publish every %d, gen %d\n", v, cnt, l.grid, LO.total, LO.rs[0], LO.rs[1], LO.rs[2], l.pint, b->gen); fflush(stderr); }
+        if (dbg) { fprintf(stderr, "[g2g] v6 variant %d: %d strips, grid %d, lds %d (rings %d / %d entries + tail %d), publish every %d, gen %d\n", v, cnt, l.grid, LO.total, LO.rs[0], LO.rs[1], LO.rtail, l.pint, b->gen); fflush(stderr); }
         snprintf(done, sizeof done, "v6 variant %d", v);
         hipLaunchKernelGGL(G2G_KERNEL[slot].v6, dim3(l.grid), dim3(l.block), l.lds, vs, probs, tiles, cnt,
                            batch_qhead(b, slot), b->d_flags, b->gen, LO, l.pint, l.pro_off, scr, batch_twin(b, slot), l.twin_dw);

@@ -26,12 +26,7 @@
 // byte offsets of the LDS regions of a v3 launch (host: v3_lds_plan)
 struct V3Lds { int rows, black, stsc, aglen, afreq, boff, bglen, bfreq, svals, sink, total; };
 
-G2G_HD inline int v3_pitch(int nslot, int lsz)            // dwords per LDS row: odd number of 16-B units
-{
-    int p = nslot * lsz;
-    if (((p >> 2) & 1) == 0) p += 4;
-    return p;
-}
+#include "g2g_lds.h"                // v3_pitch: dwords per LDS row of dynamic lists (shared with the host's plans)
 
 
 

@@ -42,13 +42,7 @@ __device__ unsigned long long g2g_v6_stamp_acc[16];
 #define V6_STAMP_PASS
 #endif
 
-// byte offsets; ringk / ringf / rs: per view (s, t, r) the key and freq arrays of the column-list ring and its entries (power of 2)
-struct V6Lds { int rows, black, stsc, svals, sink, total; int ringk[3], ringf[3], rs[3]; };
-
-#define V6_FEED 16                      // columns per ring refill
-#define V6_AHEAD 32                     // a refill reaches this many columns beyond lane 0's
-#define V6_WINDOW (64 + V6_AHEAD + 4)   // columns whose lists must fit the ring together
-#define V6_RHCOLS 128                   // columns of the per-column array of r-list heads (a power of 2 >= V6_WINDOW)
+#include "g2g_lds.h"                    // V6Lds (the launch's LDS plan), V6_FEED / V6_AHEAD / V6_WINDOW / V6_RHCOLS, v6_inline_dw
 
 // ---- where the dynamic lists of a strip live ---------------------------------------------------------------
 // A record's list may be as long as its side has gap states (hetero + 1 dwords), but 99.98 % of the lists of a refinement sweep
@@ -58,7 +52,7 @@ struct V6Lds { int rows, black, stsc, svals, sink, total; int ringk[3], ringf[3]
 // already handled "beyond the register head" ever gets there -- the scans, the stores of a long newdelta result, the strip
 // hand-over of a long list -- always behind a wave-uniform test.  A wave reads back only what it wrote itself, after a
 // s_waitcnt vmcnt(0).  LDS per strip drops from 31-45 KB (and more) to 26-30 KB.
-G2G_HD inline int v6_inline_dw(int cap4) { return cap4 <= 4 ? 4 : cap4 <= 16 ? 8 : cap4 <= 32 ? 16 : cap4 <= 64 ? 32 : cap4; }
+// (v6_inline_dw: g2g_lds.h)
 struct LS6 { const lu32 *rows0; GLB unsigned *tw; int ia, ib; };          // first dword of the rows, the twin image, inline dwords per side
 __device__ __forceinline__ GLB unsigned *ls6_twin(const LS6 &W, const lu32 *p, const int k) { return W.tw + 2 * (int) (p - W.rows0) + k; }
 __device__ __forceinline__ unsigned ls6_rd(const LS6 &W, const lu32 *p, const int k, const int I) { return k < I ? p[k] : *ls6_twin(W, p, k); }
@@ -235,15 +229,27 @@ __device__ __forceinline__ void nd6_fin(const ND6 &s, const bool was_on, lu32 *d
 
 // ---- the ring of b's static lists ------------------------------------------------------------------------
 // Per view two arrays: lookup keys (u32, (glen << 16) | 0xFFFF) and freq (f64) -- 12 bytes per entry, terminators left out.
-// An entry's ring index is its COMPACT pool position & mask: pool position minus the terminators in front of it, i.e.
+// An entry's place is its COMPACT pool position: pool position minus the terminators in front of it, i.e.
 // off[v][n + 1] - (n + 1) + k for entry k of column n (every position contributes exactly one terminator).  A lane knows its
 // column's lists by (start, length) taken from the offset tables.
+// The ring has S entries (any multiple of 32: what the launch's lists need, g2g_plan.h) and behind them a MIRRORED TAIL of T
+// entries: what is written to slot i < T is written to slot S + i as well.  A position is reduced to a slot p < S ONCE, where
+// the list's start is taken (v6_ring_slot); entry k of the list is then ring[p + k] without a wrap for every k < T -- the reads
+// past a lane's own list end that the merge loops make and mask by a select included (k runs to the wave's longest list at
+// most, and T is above the longest list of the launch).
 struct SE6 { int g; unsigned key; double f; };
-struct Ring6 { const lu32 *k; const lf64 *f; int mask; };
-__device__ __forceinline__ SE6 se6_read(const Ring6 &r, const int idx)
+struct Ring6 { const lu32 *k; const lf64 *f; };
+__device__ __forceinline__ SE6 se6_read(const Ring6 &r, const int i)
 {
-    const int i = idx & r.mask;
     SE6 e; e.key = r.k[i]; e.f = r.f[i]; e.g = (int) (e.key >> 16); return e;
+}
+// slot of compact position c: base is wave-uniform, at or below the position of the lowest live column's list and less than S
+// below it (v6_strip's refill keeps it there), and everything live spans less than S entries: c - base < 2 S, so the slot is
+// c - base or c - base - S, whichever does not wrap below zero (the unsigned minimum, as in dh_ent)
+__device__ __forceinline__ int v6_ring_slot(const int c, const int base, const int S)
+{
+    const unsigned x = (unsigned) (c - base);
+    return (int) __builtin_elementwise_min(x, x - (unsigned) S);
 }
 
 // the row's static lists in registers: glen as lookup key ((g << 16) | 0xFFFF; slots behind the list: key 0xFFFF, freq 0) and freq;
@@ -252,7 +258,7 @@ __device__ __forceinline__ SE6 se6_read(const Ring6 &r, const int idx)
 template <int N> struct A6 { const unsigned (&sk)[N]; const double (&sf)[N]; const unsigned (&tk)[N]; const double (&tf)[N]; double rhf; int ls, lt; };
 // the lane's column: rings of its s and t lists, list starts (compact), lengths.  The r view has no ring: r = [head {glen 0, freq rhf}, if the
 // column has one (lenr > lent)] + the t entries with glen + 1 (DevSide::r_from_t, checked by the host); rhf comes from a per-column array
-struct B6 { Ring6 rs, rt; int os, ot, lens, lent, lenr; double rhf; };
+struct B6 { Ring6 rs, rt; int os, ot, lens, lent, lenr; double rhf; };          // (os, ot: ring SLOTS of the lists' first entries)
 
 // one "X" merge: cf = the column's s list (ring, stretched by dlb of the record), df = a row list in registers (stretched by
 // dla): newgap(b.s, dlb, a.t|a.r, dla).  RV: df is the r view = an optional head entry {glen 0, freq hf} followed by the t
@@ -581,26 +587,45 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
     while (__ballot(ls > TAs)) ++TAs;
     while (__ballot(lt > TAt)) ++TAt;
     // ---- the ring of the columns' static lists
-    Ring6 ring[3];
+    Ring6 ring[2];
 #pragma unroll
-    for (int v = 0; v < 3; ++v) { ring[v].k = (const lu32 *) (lds + LO.ringk[v]); ring[v].f = (const lf64 *) (lds + LO.ringf[v]); ring[v].mask = LO.rs[v] - 1; }
+    for (int v = 0; v < 2; ++v) { ring[v].k = (const lu32 *) (lds + LO.ringk[v]); ring[v].f = (const lf64 *) (lds + LO.ringf[v]); }
+    const int RS0 = LO.rs[0], RS1 = LO.rs[1], RT = LO.rtail;          // entries of the s and t rings, of their mirrored tails
+    // ring bases (compact positions, wave-uniform): slot 0 of a ring is the strip's first column's list start, and a base moves
+    // on by the ring's size when the lowest live column's list starts a whole ring beyond it
+    int rbase0 = __builtin_amdgcn_readfirstlane(boff0[cbase + 1]) - (cbase + 1), rbase1 = __builtin_amdgcn_readfirstlane(boff1[cbase + 1]) - (cbase + 1);
     int fedcol = cbase - 1;                                // columns <= fedcol are in the ring
     lf64 *const rhring = (lf64 *) (lds + LO.ringf[2]);     // head freq of the r list of column c at [c & (V6_RHCOLS - 1)] (-1: no head)
-    auto refill = [&](int upto) {                          // wave-uniform; lane <-> column, one view after the other (the view is a
-        if (upto > b.right - 1) upto = b.right - 1;        // compile-time index: a per-lane choice among the descriptor's fields
-#pragma unroll                                             // turns its register copy into an indexed object in scratch memory)
+    auto refill = [&](const int n0_) {                     // n0_: lane 0's column.  Wave-uniform; lane <-> column, one view after the
+        int upto = n0_ + V6_AHEAD;                         // other (the view is a compile-time index: a per-lane choice among the
+        if (upto > b.right - 1) upto = b.right - 1;        // descriptor's fields turns its register copy into an indexed object in scratch memory)
+        {   // the lowest column any lane still reads: lane 63's (no row starts left of cbase)
+            int clow = n0_ - 63;
+            if (clow < cbase) clow = cbase;
+            if (clow > b.right - 1) clow = b.right - 1;
+            const int l0 = __builtin_amdgcn_readfirstlane(boff0[clow + 1]) - (clow + 1), l1 = __builtin_amdgcn_readfirstlane(boff1[clow + 1]) - (clow + 1);
+            while (l0 - rbase0 >= RS0) rbase0 += RS0;
+            while (l1 - rbase1 >= RS1) rbase1 += RS1;
+        }
+#pragma unroll
         for (int v = 0; v < 2; ++v) {
             const GLB int *bo = v == 0 ? boff0 : boff1;
             const GLB int *bgl = glb(b.glen[v]);
             const GLB double *bfr = glb(b.freq[v]);
             lu32 *rk = (lu32 *) (lds + LO.ringk[v]);
             lf64 *rf = (lf64 *) (lds + LO.ringf[v]);
-            const int mask = LO.rs[v] - 1;
+            const int S = v == 0 ? RS0 : RS1, base = v == 0 ? rbase0 : rbase1;
             for (int c0_ = fedcol + 1; c0_ <= upto; c0_ += 64) {
                 const int col = c0_ + lane;
                 if (col <= upto) {
                     const int k0 = bo[col + 1], len = bo[col + 2] - k0 - 1, c = k0 - (col + 1);
-                    for (int e = 0; e < len; ++e) { rk[(c + e) & mask] = v6_key(bgl[k0 + e]); rf[(c + e) & mask] = bfr[k0 + e]; }
+                    for (int e = 0; e < len; ++e) {
+                        const int i = v6_ring_slot(c + e, base, S);
+                        const unsigned key = v6_key(bgl[k0 + e]);
+                        const double f = bfr[k0 + e];
+                        rk[i] = key; rf[i] = f;
+                        if (i < RT) { rk[S + i] = key; rf[S + i] = f; }            // the mirrored tail
+                    }
                 }
             }
         }
@@ -659,7 +684,7 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
     StripSync S = strip_sync(prog_up, prog_self, dbg, failp, pgen, ti);
     if (lane < 28) stsc[lane] = 0;
     team_sync();
-    refill(cbase + V6_AHEAD);
+    refill(cbase);
     strip_need<V6Strip>(S, cbase + 1 <= c1 ? cbase + 1 : cbase);
     {
         unsigned rh = 0, rg = 0, rg2 = 0;
@@ -731,7 +756,7 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
         if (p_act) trace[p_tri] = (uint8_t) p_trb;
         if (wr_rows && s > 0) flush_rows(n0 - 1 - llast);
         if (prog_self && s > 0 && (s & (pint - 1)) == 0) strip_publish<V6Strip>(S, n0 - llast);
-        if ((s & (V6_FEED - 1)) == 0) { V6_MARK(2) refill(n0 + V6_AHEAD); team_sync(); }
+        if ((s & (V6_FEED - 1)) == 0) { V6_MARK(2) refill(n0); team_sync(); }
         if ((s & 63) == 0) { V6_MARK(3) simblk_fill(P, SB, (s >> 6) + 1, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         // -- hand-over from the row above
         hd = hu;
@@ -760,7 +785,7 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
             const bool do_hori = n > b.left;
             B6 B;
             B.rs = ring[0]; B.rt = ring[1];
-            B.os = os_cur - (n + 1); B.ot = ot_cur - (n + 1);                                     // compact positions (see Ring6)
+            B.os = v6_ring_slot(os_cur - (n + 1), rbase0, RS0); B.ot = v6_ring_slot(ot_cur - (n + 1), rbase1, RS1);      // compact positions -> slots, once per cell (see Ring6)
             B.lens = oe_cur - os_cur - 1; B.lent = te_cur - ot_cur - 1;
             { const double hv = rhring[n & (V6_RHCOLS - 1)]; B.rhf = hv >= 0 ? hv : 0.; B.lenr = B.lent + (hv >= 0 ? 1 : 0); }
             const bool up_in = do_vert && (n - (m - 1) <= P.up);          // cell (m-1, n) exists

@@ -1,15 +1,17 @@
 // g2g_plan.h -- the host-side decisions of a batch run as plain values: which variant slot is which kernel, how the CUs are
-// shared out, the list of persistent launches, and the text of a time-out report.  Plain C++17 without HIP types (it
-// compiles with g++: tests/host/plan_main.cc pins all of it without a GPU); g2g_engine.hip executes what is planned here.
+// shared out, the list of persistent launches, the text of a time-out report, and the LDS plan of the v6 launches.  Plain C++17 without HIP types (it
+// compiles with g++: tests/host/plan_main.cc and v6_layout_main.cc pin all of it without a GPU); g2g_engine.hip executes what is planned here.
 #ifndef G2G_PLAN_H
 #define G2G_PLAN_H
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
+#include "g2g_lds.h"                 // V6Lds, the v6 window constants, v3_pitch, v6_inline_dw (shared with the kernels)
 
 #define G2G_NVAR 32                 // variant slots
 #define G2G_PLAN_HDR 24             // G2G_HDR of g2g_strip.h (the engine asserts that they agree)
@@ -395,4 +397,73 @@ static inline std::string timeout_report_text(const TimeoutView &t)
     buf[o] = 0;
     return buf;
 }
+
+// ---- (e) the LDS plan of a v6 launch -------------------------------------------------------------------------------
+// Ring rows of dynamic lists, black lists, staging scalars, the rings of b's static lists, queue scratch, sinks (V6Lds and
+// the window constants: g2g_lds.h).
+// A ring is indexed by COMPACT pool position (pool position minus the terminators in front of it) modulo its size S.  S is the
+// need of the DP -- the most list entries any V6_WINDOW consecutive columns of b hold -- rounded up to 32 entries, not to a
+// power of two: the kernel reduces a position with a wave-uniform base and one conditional subtract (no mask, no division), and a
+// MIRRORED TAIL of T entries behind the S (a copy of slots [0, T)) lets it read a list that starts at slot p < S as ring[p + k]
+// without a wrap, for every k a merge loop asks for: k runs up to the wave's longest list, so T is the longest list of any view
+// plus one, rounded up to 4.
+struct V6Ring {
+    int rs[3];                      // ring entries per view (s, t; r: V6_RHCOLS head freqs, one per column, no ring)
+    int tail;                       // entries of the mirrored tail
+    int need[3];                    // what rs was rounded up from
+};
+// off[v]: the offset table of view v of b's static lists (column c's list is [off[v][c + 1], off[v][c + 2]), terminator included)
+static inline V6Ring v6_ring_need(const int32_t *const off[3], int left, int right)
+{
+    V6Ring R;
+    int longest = 0;
+    for (int v = 0; v < 3; ++v) {
+        int need = 1;
+        for (int c = left; c < right; ++c) {
+            const int e = std::min(c + V6_WINDOW, right);
+            need = std::max(need, (off[v][e + 1] - (e + 1)) - (off[v][c + 1] - (c + 1)));
+            longest = std::max(longest, off[v][c + 2] - off[v][c + 1] - 1);
+        }
+        R.need[v] = need;
+        R.rs[v] = v < 2 ? std::max(32, (need + 31) & ~31) : V6_RHCOLS;
+    }
+    R.tail = (longest + 1 + 3) & ~3;
+    return R;
+}
+// the plan of a launch: the largest S per view and the largest T of its DPs, each taken separately
+static inline void v6_ring_max(V6Ring &into, const V6Ring &r)
+{
+    for (int v = 0; v < 3; ++v) { into.rs[v] = std::max(into.rs[v], r.rs[v]); into.need[v] = std::max(into.need[v], r.need[v]); }
+    into.tail = std::max(into.tail, r.tail);
+}
+static inline V6Lds v6_layout(int rows_bytes, int ca4max, const V6Ring &R)
+{
+    V6Lds L;
+    int o = 0;
+    auto take = [&](int bytes) { int r = o; o = (o + bytes + 15) & ~15; return r; };
+    L.rows = take(rows_bytes);
+    L.black = take(4 * (ca4max + 8));
+    L.stsc = take(4 * 28);
+    L.rtail = R.tail;
+    for (int v = 0; v < 3; ++v) { L.rs[v] = R.rs[v]; L.ringf[v] = take(8 * (R.rs[v] + (v < 2 ? R.tail : 0))); }
+    for (int v = 0; v < 3; ++v) L.ringk[v] = take(v < 2 ? 4 * (R.rs[v] + R.tail) : 0);      // (view 2: an array of head freqs per column, no keys)
+    L.svals = take(4 * 64);
+    L.sink = take(4 * 64 + 16 * 64);
+    L.total = o;
+    return L;
+}
+static inline int v6_rows_bytes(int capa, int capb, int noll)
+{
+    const int lsz = v6_inline_dw((capa + 3) & ~3) + v6_inline_dw((capb + 3) & ~3);      // the INLINE parts of a record's two lists (LS6)
+    return 65 * v3_pitch(noll == 3 ? 9 : 6, lsz) * 4 + 32;
+}
+// A launch has ONE LDS plan, the largest of its DPs, and LDS decides how many strips a CU holds (the kernel takes a whole SIMD's
+// registers: four per CU at most).  Class A (up to 40 KB, four strips per CU) is the default limit of v6: with a larger plan in
+// the launch every strip of it drops to three per CU, and in a launch of their own the large DPs are bound by their critical
+// path (measured when rings were powers of two: the bench sweep took 709-738 ms with limits of 46-49 KB against 660 ms at 40 KB).
+// With rings of the size the lists need (and a window of 88 columns) every _pf DP of the bench sweep fits class A -- the 16
+// balanced divisions whose 513-807 t entries used to take a 1024-entry ring and ran on the 8-lanes-per-cell kernel for it
+// included (37-40 KB now; the rest of the sweep: up to 35 KB).  Classes B (up to V6_SMALL_KB) and C (V6_LARGE_KB) stay as
+// options for measurements.
+static const int V6_CLASS_A = 40 * 1024;
 #endif
