@@ -77,7 +77,7 @@ struct DevProb {
     int      v2_rowstride;
     double  *v2_sim;       // sim2 of every in-band cell, row-major, row m at v2_rowoff[m - a.left] (- nlo(m))
     long long *v2_rowoff;
-    int      v2_ok;      // 1: handled by g2g_forward_kernel_v2
+    int      v2_ok;      // kernel generation: 0 g2g_forward_kernel, 1 v2, 2 v3 with LDS lists, 3 v3r, 6, 7, 8 (G2GFamily of g2g_plan.h)
     // trace
     uint8_t *trace;
     int      tstride;

@@ -439,71 +439,6 @@ static inline unsigned *&batch_twin(g2g_batch *b, int slot) { return b->twin[var
 static inline size_t &batch_twin_cap(g2g_batch *b, int slot) { return b->twin_cap[variant_v6_index(slot)]; }
 static inline int *batch_qhead(g2g_batch *b, int slot) { return slot < G2G_HDR ? b->d_flags + slot : b->d_flags + b->xq_off + (slot - G2G_HDR); }
 
-// LDS footprint of g2g_forward_kernel_v2 for one problem (see V2Geom): (slots * R + extras) records
-static size_t v2_lds_bytes(int kind, int noll, int capa, int capb, int mla, int mlb, int threads = G2G_V2_THREADS)
-{
-    const size_t recsz = (16 + 4 * (size_t) (capa + (kind == 2 ? capb : 0)) + 15) & ~(size_t) 15;
-    const size_t R = threads / 8;
-    const size_t lists = (size_t) 10 * 3 * (R * mla + (kind == 2 ? (R + 2) * mlb : 0)) + 8;   // glen i16 + freq f64
-    return (((noll == 3 ? 9 : 6) * R + 5) * recsz + 16 * R + lists + 16 + 15) & ~(size_t) 15;
-}
-
-// LDS plan of the v3 kernel (g2g_kernels_v3.hip) for one problem with C-column tiles: ring rows, the black
-// list, staging scalars, and the static-list pools of a strip's rows / a block's columns
-static V3Lds v3_layout(int rows_bytes, int ca4max, int apool, int bpool, int C)
-{
-    V3Lds L;
-    int o = 0;
-    auto take = [&](int bytes) { int r = o; o = (o + bytes + 15) & ~15; return r; };
-    L.rows = take(rows_bytes);
-    L.black = take(4 * (ca4max + 4));
-    L.stsc = take(4 * 28);
-    L.aglen = take(4 * (apool + 4));
-    L.afreq = take(8 * (apool + 4));
-    L.boff = take(bpool ? 4 * 3 * C : 0);
-    L.bglen = take(bpool ? 4 * (bpool + 4) : 0);
-    L.bfreq = take(bpool ? 8 * (bpool + 4) : 0);
-    L.svals = take(4 * 64);
-    L.sink = take(4 * 64);
-    L.total = o;
-    return L;
-}
-// LDS plan of the v6 kernel: V6Ring, v6_ring_need, v6_layout, v6_rows_bytes and the footprint class A live in g2g_plan.h
-static int v6_small_lds(const g2g_ctx *c) { const char *e = g2g_opt(c, "V6_SMALL_KB"); return e ? atoi(e) * 1024 : 40 * 1024; }
-#define V6_SMALL_LDS (v6_small_lds(ctx))
-static int v6_large_lds(const g2g_ctx *c) { const char *e = g2g_opt(c, "V6_LARGE_KB"); return e ? atoi(e) * 1024 : 0; }
-#define V6_LARGE_LDS (v6_large_lds(ctx))
-static int v6_rows_bytes(const DevProb &d) { return v6_rows_bytes(d.capa, d.capb, d.noll); }
-static V6Ring v6_ring_need(const g2g_problem *p) { return v6_ring_need(p->b.gfq.off, p->b.left, p->b.right); }
-struct V3Need { int rows_bytes, ca4, apool, bpool, total; };
-static V3Need v3_need(const DevProb &d, const g2g_problem *p, int C, bool areg = false)
-{
-    V3Need n;
-    const int capb = d.kind == 2 ? d.capb : 0;
-    n.ca4 = (d.capa + 3) & ~3;
-    const int lsz = n.ca4 + ((capb + 3) & ~3);
-    n.rows_bytes = 65 * v3_pitch(d.noll == 3 ? 9 : 6, lsz) * 4;
-    n.apool = 0; n.bpool = 0;
-    const int al = p->a.left, ar = p->a.right, bl = p->b.left, br = p->b.right;
-    for (int m0 = al; m0 < ar; m0 += 64) {
-        const int me = std::min(m0 + 64, ar);
-        int c = 0;
-        for (int v = 0; v < 3; ++v) c += p->a.gfq.off[v][me + 1] - p->a.gfq.off[v][m0 + 1];
-        n.apool = std::max(n.apool, c);
-    }
-    if (d.kind == 2)
-        for (int c0 = bl; c0 < br; c0 += C) {
-            const int c1 = std::min(c0 + C, br);
-            int c = 0;
-            for (int v = 0; v < 3; ++v) c += p->b.gfq.off[v][c1 + 1] - p->b.gfq.off[v][c0 + 1];
-            n.bpool = std::max(n.bpool, c);
-        }
-    if (d.kind == 2 && !n.bpool) n.bpool = 1;
-    if (areg) n.apool = 0;                                  // the rows' static lists live in registers
-    n.total = v3_layout(n.rows_bytes, n.ca4, n.apool, n.bpool, C).total;
-    return n;
-}
-
 static int kind_of(int alnmode)
 {
     switch (alnmode) {
@@ -688,196 +623,247 @@ static void release_arena(g2g_batch *b)
     b->d_arena = 0;
 }
 
-// Which kernel generation runs a DP (DevProb::v2_ok): 0 g2g_forward_kernel, 1 v2, 2 v3 with LDS lists, 3 v3r, 6, 7, 8; *ib: on a
-// bonus-aware instantiation of it.
-static int choose_kernel(const g2g_ctx *ctx, const g2g_batch *b, const DevProb &d, const g2g_problem *p, bool force_v1, char *ib)
+// ---- g2g_batch_prepare: its steps ------------------------------------------------------------------------------------------
+// What is decided -- the shape of the batch, the kernel of each DP, the queues -- is decided in g2g_plan.h from plain values
+// (PrepOptions, DpFacts); the functions here pack, carve the arena, allocate and upload.
+static_assert(G2G_PLAN_V2_TILE_COLS == G2G_V2_TILE_COLS, "g2g_plan.h and the build flags disagree about the widest v2 tile");
+static PrepOptions prep_options(const g2g_ctx *c)
 {
-    // v2 kernel (gap-profile engines): packed 16-bit gap lengths and an LDS budget decide eligibility
-    int gen = 0;
-    if (d.kind == 0 && !d.rect && !force_v1 && !g2g_opt(ctx, "FORCE_V1") && !g2g_opt(ctx, "NO_V7")) gen = 7;      // DPunit: strips without gap state (the rectangular engine: g2g_forward_kernel)
-    if (d.kind == 3 && !force_v1 && !g2g_opt(ctx, "FORCE_V1") && !g2g_opt(ctx, "NO_V8")) {
-        // DPunit_nv: strips with the members' gap lengths in registers, for the member counts selAlnMode sends this way
-        const int an = p->a.many, bn = p->b.many, ck = p->crg2_kind;
-        const bool fits = ck == 11 ? (an == 1 && bn == 1) : (ck == 120 || ck == 121) ? (an == 1 && bn <= 5) :
-                          (ck == 210 || ck == 211) ? (an <= 5 && bn == 1) : (ck == 220 || ck == 221) ? (an <= 3 && bn <= 3) : false;
-        if (fits && p->a.gapdens && p->b.gapdens && p->a.postgapdens && p->b.postgapdens && (!(ck & 1) || ck == 11 || (p->a.weight && p->b.weight))) gen = 8;
-    }
-    if ((d.kind == 1 || d.kind == 2) && !force_v1 && !g2g_opt(ctx, "FORCE_V1") && p->a.len + p->b.len < 65000) {
-        // _pf: one lane per cell with rank-form merges (v6) when the rows' static lists fit the register file
-        if (b->v6_on && !g2g_opt(ctx, "FORCE_V2") && !g2g_opt(ctx, "NO_V6") && d.kind == 2 && d.a.maxlist <= (d.noll == 3 ? G2G_V6_NA3 : G2G_V6_NA) && d.a.r_from_t && d.b.r_from_t &&
-            v6_layout(v6_rows_bytes(d), (d.capa + 3) & ~3, v6_ring_need(p)).total <= std::max(V6_SMALL_LDS, V6_LARGE_LDS)) gen = 6;
-        else if (!g2g_opt(ctx, "FORCE_V2") && !g2g_opt(ctx, "NO_AREG") && d.kind == 1 && d.a.maxlist <= G2G_V3_NA && d.a.r_from_t &&
-            v3_need(d, p, b->v3_cols, true).total <= (int) V2_LDS_MAX) gen = 3;
-        else {
-            // lists too long for registers: the LDS-list one-lane-per-cell kernel, unless its LDS footprint leaves fewer than
-            // three waves per CU and the 8-lanes-per-cell kernel fits (a 512 x 2048 nt DNA sweep with 17-32 entry lists and
-            // Noll 3: 87 KB per strip; 28.3 s with it, 22.4 s on v2)
-            // (v2 caches static gap lengths as SIGNED 16-bit with negative = terminator: a gap run can be as long as the
-            // group has columns, so sides of 32768 columns or more are not eligible -- they stay on v3 / v1, which keep 32 bits)
-            const bool v2fit = std::max(p->a.len, p->b.len) < 32768 &&
-                v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, b->v2_threads) + 4 * b->v2_threads <= V2_LDS_MAX;
-            const int v3tot = (!g2g_opt(ctx, "FORCE_V2") && d.kind == 1) ? v3_need(d, p, b->v3_cols).total : (int) V2_LDS_MAX + 1;
-            if (v3tot <= (int) V2_LDS_MAX && (v3tot <= (int) V2_LDS_MAX / 3 || !v2fit || g2g_opt(ctx, "NO_AREG"))) gen = 2;
-            else if (v2fit) gen = 1;
-        }
-    }
-    if (d.nbonus) {
-        // The intron-position bonus: g2g_forward_kernel (v1), and the bonus-aware instantiations of the strips without gap
-        // state (v7), of the naive-record strips (v8) and of the 8-lanes-per-cell strips (v2, sweep mode) -- not v3 / v3r / v6
-        // (register-bound), so an annotated _hf / _pf DP goes to v2 whatever would otherwise have claimed it, within v2's own
-        // limits.  NO_STRIP_BONUS: v1 for all of them, as before the strips knew the bonus.
-        const int was = gen;
-        gen = 0;
-        if (!g2g_opt(ctx, "NO_STRIP_BONUS")) {
-            if (was == 7 || was == 8) gen = was;
-            else if (was >= 1 && was <= 6 && (d.kind == 1 || d.kind == 2) && b->v2_sweep && std::max(p->a.len, p->b.len) < 32768 &&
-                     v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, b->v2_threads) + 4 * b->v2_threads <= V2_LDS_MAX) gen = 1;
-        }
-        *ib = gen ? 1 : 0;
-    }
-    return gen;
+    PrepOptions o = prep_defaults(c->ncu);
+    auto on = [&](const char *name) { return g2g_opt(c, name) != 0; };
+    auto num = [&](const char *name, int unset) { const char *e = g2g_opt(c, name); return e ? atoi(e) : unset; };
+    o.force_v1 = on("FORCE_V1"); o.no_v7 = on("NO_V7"); o.no_v8 = on("NO_V8"); o.force_v2 = on("FORCE_V2"); o.no_v6 = on("NO_V6");
+    o.no_areg = on("NO_AREG"); o.no_strip_bonus = on("NO_STRIP_BONUS"); o.no_chainq = on("NO_CHAINQ"); o.no_simblk = on("NO_SIMBLK");
+    o.v6_small = num("V6_SMALL_KB", 40) * 1024; o.v6_large = num("V6_LARGE_KB", 0) * 1024;
+    o.v2_threads = num("V2_THREADS", 0); o.v2_cols = num("V2_COLS", 0); o.v3_cols = num("V3_COLS", 0);
+    if (const char *e = g2g_opt(c, "V6_MIN_STRIPS")) { o.min_strips_set = true; o.min_strips = atoll(e); }
+    o.v3_sweep = num("V3_SWEEP", 1); o.v2_sweep = num("V2_SWEEP", 1);
+    if (const char *e = g2g_opt(c, "INJECT_STALL")) { o.inject = true; o.inject_victim = atoi(e); }
+    return o;
 }
 
-// v2 tiles: (strip i of R rows) x (block j of C columns, C chosen per batch); per kernel variant one queue
-// ordered by wavefront i + j; one completion flag per tile slot (empty slots count as done for ever)
-// (g2g_batch_free has taken the batch when this fails)
-static int build_queues(g2g_ctx *ctx, g2g_batch *b, const g2g_problem *const *prob)
+// (new g2g_batch() zero-initialises every plain member: counters, device pointers, pool capacities, offsets)
+static g2g_batch *new_batch(g2g_ctx *ctx, int n, const g2g_problem *const *prob, bool force_v1, const PrepOptions &o)
 {
-    const int n = b->n;
-    b->d_tiles = 0; b->tiles_cap = b->flags_cap = 0; b->d_idxp = 0; b->np = 0; b->ntiles = 0; b->lds2p = 0; b->v2_maxrows = 1; b->v2_maxcols = 1; b->simtile_lds = 0; b->d_flags = 0; b->nflags = 0; b->gen = 0;
-    std::vector<std::vector<std::vector<V2Tile> > > q(G2G_NVAR);  // [variant][wavefront] -> tiles
-    std::vector<int> flags(G2G_HDR + G2G_HDRN, 0);           // queue heads, then the header of the waits (g2g_wait_ge)
-    std::vector<V2Tile> pre[G2G_NVAR];                // boundary chains of sweep-mode DPs: they head their variant's queue
-    std::vector<int> ip;                              // the other DPs: chains in the prologue kernel
-    const bool chainq = !g2g_opt(ctx, "NO_CHAINQ");
-    int v6rows[6] = {0, 0, 0, 0, 0, 0}, v6ca4[6] = {0, 0, 0, 0, 0, 0};
-    V6Ring v6rs[6];
-    for (int v = 0; v < 6; ++v) { const V6Ring r0 = {{32, 32, V6_RHCOLS}, 4, {1, 1, 1}}; v6rs[v] = r0; }
-    V3Need need[8];
-    memset(need, 0, sizeof need);
+    g2g_batch *b = new g2g_batch();
+    b->ctx = ctx; b->n = n; b->force_v1 = force_v1; b->injected = o.inject;
+    b->src.assign(prob, prob + n);
+    b->recovered.assign(n, g2g_result()); b->was_recovered.assign(n, 0); b->ib.assign(n, 0); b->path_rec.assign(n, 0);
+    b->dp.resize(n); b->status.assign(n, G2G_OK); b->cells.assign(n, 0); b->out_off.assign(n, 0); b->tcap.assign(n, 0); b->rr1.assign(n, 0);
+    b->v2_maxrows = b->v2_maxcols = 1;
+    return b;
+}
+
+// size the staging buffer once (growing a pinned buffer means allocating and copying it again)
+static size_t staging_estimate(const g2g_ctx *ctx, int n, const g2g_problem *const *prob)
+{
+    auto side_bytes = [&](const g2g_side &s) {
+        const size_t cols = (size_t) s.len + 2;
+        const g2g_side_dev *tw = (s.dev && s.dev->ctx == ctx) ? s.dev : 0;
+        size_t t = 8 * (size_t) s.many + 24 * cols + 256;
+        if (!(tw && tw->seq)) t += cols * s.many;
+        if (s.pseq && s.nelm > 0 && !(tw && tw->pseq)) t += 8 * cols * s.nelm;
+        if (s.has_gfq) for (int v = 0; v < 3; ++v) if (s.gfq.off[v] && !(tw && tw->freq[v])) t += 4 * cols + 12 * (size_t) s.gfq.off[v][s.len + 1] + 64;
+        if (s.gapdens) t += 16 * cols * s.many;
+        return t;
+    };
+    size_t est = (sizeof(DevProb) + 8) * (size_t) (n > 0 ? n : 1) + 4096;
     for (int i = 0; i < n; ++i) {
+        const g2g_problem *p = prob[i];
+        if (check_problem(p) != G2G_OK) continue;
+        est += side_bytes(p->a) + side_bytes(p->b) + 8 * (size_t) (p->simmtx ? p->simdim * p->simrows : 0) + 64;
+    }
+    return est;
+}
+
+// the intron-position bonus table of a DP, with the strip kernels' per-row index behind bon_m's entries
+static void pack_bonus(Blob &bl, const g2g_problem *p, DevProb &d)
+{
+    std::vector<BonusCell> bc;
+    intron_bonus_table(p, bc);
+    if (bc.empty()) return;
+    std::vector<int> bm, bn; std::vector<double> bh, bx;
+    for (const BonusCell &c : bc) { bm.push_back(c.m); bn.push_back(c.n); bh.push_back(c.h); bx.push_back(c.mx); }
+    d.nbonus = (int) bc.size();
+    // first entry of row a.left + r, r = 0 .. rows (the table is row-major with n ascending within a row; g2g_forward_kernel
+    // reads the first nbonus entries only)
+    const int rows = p->a.right - p->a.left;
+    size_t k = 0;
+    for (int r = 0; r <= rows; ++r) {
+        while (k < bc.size() && bc[k].m < p->a.left + r) ++k;
+        bm.push_back((int) k);
+    }
+    // (put_now: the four vectors are gone by the time flush() makes put()'s deferred copies)
+    d.bon_m = OFF<const int>(bl.put_now(bm.data(), sizeof(int) * bm.size()));
+    d.bon_n = OFF<const int>(bl.put_now(bn.data(), sizeof(int) * bn.size()));
+    d.bon_h = OFF<const double>(bl.put_now(bh.data(), sizeof(double) * bh.size()));
+    d.bon_mx = OFF<const double>(bl.put_now(bx.data(), sizeof(double) * bx.size()));
+}
+
+// 1. check a problem and pack its inputs into the host image; returns its status (d.kind -1: not run)
+static int pack_problem(Blob &bl, const g2g_problem *p, DevProb &d, std::vector<DevPatch> &patches)
+{
+    memset(&d, 0, sizeof d);
+    const int rc = check_problem(p);
+    if (rc) { d.kind = -1; return rc; }
+    d.kind = kind_of(p->alnmode);
+    d.noll = p->noll; d.sim2_kind = p->sim2_kind; d.crg2_kind = p->crg2_kind; d.codonk1 = p->codonk1;
+    d.rect = is_rect(p->alnmode) ? 1 : 0;
+    d.lw = p->lw; d.up = p->up;
+    if (d.rect) { d.lw = p->b.left - p->a.right; d.up = p->b.right - p->a.left; }     // every cell and every boundary corner inside
+    d.width = d.up - d.lw + 3;
+    d.basic_gop = p->basic_gop; d.weighted_gop = p->weighted_gop; d.u = p->u;
+    d.u2divu1 = p->u2divu1; d.v2divv1 = p->v2divv1;
+    d.simdim = p->simdim;
+    if (p->simmtx) d.simmtx = OFF<const double>(bl.put(p->simmtx, sizeof(double) * (size_t) p->simdim * p->simrows));
+    pack_side(bl, p->a, d.a, d.kind, d.kind == 1 || d.kind == 2, patches);
+    pack_side(bl, p->b, d.b, d.kind, d.kind == 2, patches);
+    d.spb_fact = p->spb_fact; d.dvsp = p->dvsp;
+    pack_bonus(bl, p, d);
+    return G2G_OK;
+}
+
+// 2. what the decisions need of a packed DP (and the capacity of its dynamic lists, which is one of those things)
+static DpFacts dp_facts(DevProb &d, const g2g_problem *p)
+{
+    DpFacts f;
+    memset(&f, 0, sizeof f);
+    f.kind = d.kind;
+    if (d.kind < 0) return f;
+    if (d.kind == 1) { d.capa = p->a.gfq.hetero + 1; d.capb = 0; }
+    else if (d.kind == 2) { d.capa = p->a.gfq.hetero + 1; d.capb = p->b.gfq.hetero + 1; }
+    else if (d.kind == 3) { d.capa = p->a.many; d.capb = p->b.many; }
+    f.rect = d.rect; f.noll = d.noll; f.capa = d.capa; f.capb = d.capb; f.nbonus = d.nbonus;
+    f.crg2_kind = d.crg2_kind; f.sim2_kind = d.sim2_kind; f.lw = d.lw; f.up = d.up;
+    auto side = [](const g2g_side &s, const DevSide &ds) {
+        SideFacts x = {s.len, s.many, s.left, s.right, ds.nelm, ds.felm, ds.maxlist, ds.r_from_t, s.gapdens != 0, s.postgapdens != 0, s.weight != 0, {0, 0, 0}};
+        if (s.has_gfq) for (int v = 0; v < 3; ++v) x.off[v] = s.gfq.off[v];
+        return x;
+    };
+    f.a = side(p->a, d.a); f.b = side(p->b, d.b);
+    return f;
+}
+
+// 5. the device-only part of the arena: state, trace, then the outputs of all problems in ONE contiguous region (a single
+// device-to-host copy fetches a whole sweep).  Offsets go into the pointer fields (OFF) and are rebased after allocation.
+struct Arena {
+    size_t off;
+    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 15) & ~(size_t) 15; return o; }
+};
+static void layout_v1_state(Arena &A, DevProb &d)      // the diagonal-indexed row buffers of g2g_forward_kernel (v1): only for DPs it runs
+{
+    const size_t W = d.width;
+    for (int x = 0; x < NX; ++x) {
+        if (d.noll != 3 && (x == XG2 || x == XF2)) continue;
+        d.val[x] = OFF<double>(A.take(sizeof(double) * W));
+        d.dir[x] = OFF<uint8_t>(A.take(W));
+        if (d.kind == 1 || d.kind == 2) d.dla[x] = OFF<int2>(A.take(sizeof(int2) * W * d.capa));
+        if (d.kind == 2) d.dlb[x] = OFF<int2>(A.take(sizeof(int2) * W * d.capb));
+        if (d.kind == 1) d.glb[x] = OFF<int>(A.take(sizeof(int) * W));
+        if (d.kind == 3) d.glb[x] = OFF<int>(A.take(sizeof(int) * W * (d.capa + d.capb)));
+    }
+    d.spw = (int) W;
+}
+// boundary records of a DP on strips; returns whether its kernel reads a column-score matrix (strips in sweep mode make their
+// own scores, block by block)
+static bool layout_strip_state(Arena &A, DevProb &d, int blen, const BatchShape &s, const PrepOptions &o)
+{
+    const size_t rows = (size_t) (d.a.right - d.a.left);
+    d.spw = 1;                                  // g2g_spscore_kernel keeps its two dynamic lists in dla/dlb[XH] (stride spw)
+    d.dla[XH] = OFF<int2>(A.take(sizeof(int2) * (size_t) (d.capa + 1)));
+    if (d.kind == 2) d.dlb[XH] = OFF<int2>(A.take(sizeof(int2) * (size_t) (d.capb + 1)));
+    const size_t recsz = strip_record_bytes(d.v2_ok, d.kind, d.capa, d.capb);
+    d.v2_rowstride = blen + 3;
+    d.v2_rowH = OFF<void>(A.take(3 * recsz * (size_t) d.v2_rowstride));
+    d.v2_rowG = OFF<void>(A.take(3 * recsz * (size_t) d.v2_rowstride));
+    if (d.noll == 3) d.v2_rowG2 = OFF<void>(A.take(3 * recsz * (size_t) d.v2_rowstride));
+    d.v2_colH = OFF<void>(A.take(recsz * (rows + 3)));
+    d.v2_cbH = OFF<void>(A.take(recsz * (rows + 3)));
+    d.v2_cbF = OFF<void>(A.take(recsz * (rows + 3)));
+    if (d.noll == 3) d.v2_cbF2 = OFF<void>(A.take(recsz * (rows + 3)));
+    d.v2_rowoff = OFF<long long>(A.take(sizeof(long long) * (rows + 2)));
+    const bool own_sim = !o.no_simblk && (d.v2_ok >= 6 || (d.v2_ok == 1 && s.v2_sweep) || ((d.v2_ok == 2 || d.v2_ok == 3) && d.kind == 1 && s.v3_sweep));
+    if (!own_sim) d.v2_sim = OFF<double>(A.take(sizeof(double) * (size_t) d.cells + 64));
+    return !own_sim;
+}
+static void layout_arena(g2g_batch *b, const BatchShape &s, const PrepOptions &o)
+{
+    Arena A = {b->in_bytes};
+    for (int i = 0; i < b->n; ++i) {
+        DevProb &d = b->dp[i];
+        if (d.kind < 0) continue;
+        const int al = d.a.left, ar = d.a.right, bl = d.b.left, br = d.b.right;
+        const BandCells bc = band_cells(al, ar, bl, br, d.lw, d.up);
+        d.d0 = al + bl; d.d1 = (ar - 1) + (br - 1);
+        b->cells[i] = d.cells = bc.cells;
+        d.tstride = bc.tstride;
+        d.trace = OFF<uint8_t>(A.take((size_t) (d.d1 - d.d0 + 1) * d.tstride));
+        if (!d.v2_ok) layout_v1_state(A, d);
+        else if (layout_strip_state(A, d, b->src[i]->b.len, s, o)) ++b->nsimmat;
+        b->rr1[i] = (long long) (bl - al) + (br - ar);
+        b->tcap[i] = d.tcap = (ar - al) + (br - bl) + 4;
+    }
+    b->out_lo = A.off;
+    for (int i = 0; i < b->n; ++i) {
+        DevProb &d = b->dp[i];
+        if (d.kind < 0) continue;
+        b->out_off[i] = A.take(sizeof(double) + sizeof(int) * 2 + sizeof(int2) * (size_t) d.tcap);
+        d.score = OFF<double>(b->out_off[i]);
+        d.ntrace = OFF<int>(b->out_off[i] + sizeof(double));
+        d.otrace = OFF<int2>(b->out_off[i] + sizeof(double) + 2 * sizeof(int));
+    }
+    b->out_hi = A.off;
+    b->arena_bytes = A.off + 256;
+}
+
+// 6. the offsets of a descriptor become addresses
+static void rebase_problem(DevProb &d, char *base)
+{
+    rebase(d.simmtx, base);
+    rebase(d.bon_m, base); rebase(d.bon_n, base); rebase(d.bon_h, base); rebase(d.bon_mx, base);
+    rebase_side(d.a, base); rebase_side(d.b, base);
+    for (int x = 0; x < NX; ++x) { rebase(d.val[x], base); rebase(d.dir[x], base); rebase(d.dla[x], base); rebase(d.dlb[x], base); rebase(d.glb[x], base); }
+    rebase(d.v2_rowH, base); rebase(d.v2_rowG, base); rebase(d.v2_rowG2, base); rebase(d.v2_colH, base);
+    rebase(d.v2_cbH, base); rebase(d.v2_cbF, base); rebase(d.v2_cbF2, base);
+    rebase(d.v2_rowoff, base); rebase(d.v2_sim, base);
+    rebase(d.trace, base); rebase(d.score, base); rebase(d.ntrace, base); rebase(d.otrace, base);
+}
+
+// 7. index lists of the DPs on g2g_forward_kernel (i1) and on strips (i2), and the dynamic LDS of the v2 launch
+static void fill_index_lists(g2g_batch *b, int *i1, int *i2)
+{
+    b->n1 = b->n2 = 0; b->lds2 = 0;
+    for (int i = 0; i < b->n; ++i) {
         const DevProb &d = b->dp[i];
-        if (d.kind < 0 || !d.v2_ok) continue;
-        const size_t recsz = d.v2_ok == 8 ? 4 * V8_REC : (16 + 4 * (size_t) (d.capa + (d.kind == 2 ? d.capb : 0)) + 15) & ~(size_t) 15;
-        b->lds2p = std::max(b->lds2p, 5 * recsz + 64);
-        b->v2_maxrows = std::max(b->v2_maxrows, d.a.right - d.a.left);
-        b->v2_maxcols = std::max(b->v2_maxcols, d.b.right - d.b.left);
-        if (d.a.nelm > 0 && sim_tiled_kind(d.sim2_kind)) {        // a's profile rows + b's frequency vectors or residues
-            const bool vecb = d.sim2_kind == 33 || d.sim2_kind == 330;
-            b->simtile_lds = std::max(b->simtile_lds, (size_t) 8 * SIM_TR * ((d.a.nelm - d.a.felm + 1) & ~1) + (vecb ? (size_t) 8 * SIM_TC * (d.b.felm > 0 ? d.b.felm : 0) : (size_t) SIM_TC * d.b.many) + 64);
-        }
-        const int al = d.a.left, ar = d.a.right, bl_ = d.b.left, br = d.b.right;
-        const int R = d.v2_ok >= 2 ? 64 : b->v2_threads / 8;
-        const bool swp3 = (d.v2_ok == 3 || d.v2_ok == 2) && d.kind == 1 && b->v3_sweep;   // one tile per strip, pipelined (kind 1 only: no column pool)
-        const bool swp2 = (d.v2_ok == 1 && b->v2_sweep) || d.v2_ok >= 6;     // (v6 and v7 know sweep mode only)
-        const int C = (swp3 || swp2) ? (1 << 20) : d.v2_ok >= 2 ? b->v3_cols : b->v2_cols;
-        const int nstrip = (ar - al + R - 1) / R, nblk = (br - bl_ + C - 1) / C;
-        // (one LDS plan per launch = the largest of its DPs: DPs whose column lists need a big ring get a launch of their own,
-        //  or a handful of balanced divisions would cost every strip of the sweep its occupancy)
-        int v6fp = 0;                                  // footprint class A / B / C
-        if (d.v2_ok == 6) { const int tot = v6_layout(v6_rows_bytes(d), (d.capa + 3) & ~3, v6_ring_need(prob[i])).total; v6fp = tot > V6_SMALL_LDS ? 2 : tot > V6_CLASS_A ? 1 : 0; }
-        const int var = variant_slot(d.v2_ok, d.kind, d.noll, b->ib[i] != 0, v6fp);
-        if (var < 0) { g2g_set_error("%s", "g2g_batch_prepare: a DP was given a kernel that has no variant slot"); g2g_batch_free(b); return G2G_ERR_DEVICE; }
-        b->var_cells[var] += b->cells[i];
-        if (d.v2_ok == 6) {
-            const int v6cls = variant_v6_index(var);
-            v6rows[v6cls] = std::max(v6rows[v6cls], v6_rows_bytes(d));
-            v6ca4[v6cls] = std::max(v6ca4[v6cls], (d.capa + 3) & ~3);
-            v6_ring_max(v6rs[v6cls], v6_ring_need(prob[i]));
-        } else if (d.v2_ok >= 7) {
-        } else if (d.v2_ok >= 2) {
-            const V3Need nd = v3_need(d, prob[i], C, d.v2_ok == 3);
-            V3Need &x = need[variant_v3_index(var)];
-            x.rows_bytes = std::max(x.rows_bytes, nd.rows_bytes); x.ca4 = std::max(x.ca4, nd.ca4);
-            x.apool = std::max(x.apool, nd.apool); x.bpool = std::max(x.bpool, nd.bpool);
-        }
-        const bool cq = (chainq && (swp2 || swp3)) || d.v2_ok >= 7;      // (v7's and v8's chains always run as queue entries: the prologue kernel knows the gap-profile kinds only)
-        int ftop = -1, fleft = -1;
-        if (cq) {
-            ftop = (int) flags.size(); fleft = ftop + G2G_FSTRIDE;
-            flags.resize(flags.size() + 2 * G2G_FSTRIDE, 0);
-            V2Tile T;
-            T.prob = i; T.tj = 0; T.nsteps = 0; T.dep_up = T.dep_left = T.dep_diag = T.dep_war = -1;
-            T.ti = -1; T.self = ftop; pre[var].push_back(T);
-            T.ti = -2; T.self = fleft; pre[var].push_back(T);
-        } else ip.push_back(i);
-        const int fbase = (int) flags.size();
-        flags.resize(flags.size() + (size_t) nstrip * nblk * G2G_FSTRIDE, 0x7fffffff);
-        for (int ti = 0; ti < nstrip; ++ti) {
-            const int m0 = al + ti * R;
-            for (int tj = 0; tj < nblk; ++tj) {
-                const int c0 = bl_ + tj * C, c1 = std::min(c0 + C, br);
-                const int cbase = std::max(std::max(m0 + d.lw, bl_), c0);
-                int nsteps = 0;
-                for (int t = 0; t < R && m0 + t < ar; ++t) {
-                    const int m = m0 + t;
-                    const int lo = std::max(std::max(m + d.lw, bl_), c0), hi = std::min(std::min(m + d.up + 1, br), c1);
-                    if (hi > lo) nsteps = std::max(nsteps, hi - cbase + t);
-                }
-                if (!nsteps) continue;
-                V2Tile T;
-                T.prob = i; T.ti = ti; T.tj = tj; T.nsteps = nsteps;
-                T.self = fbase + (ti * nblk + tj) * G2G_FSTRIDE;
-                T.dep_up = ti > 0 ? T.self - nblk * G2G_FSTRIDE : ftop;             // sweep mode: the top chain is strip 0's "strip above"
-                T.dep_left = tj > 0 ? T.self - G2G_FSTRIDE : fleft;
-                T.dep_diag = (ti > 0 && tj > 0) ? T.self - (nblk + 1) * G2G_FSTRIDE : -1;
-                T.dep_war = (ti > 1 && tj + 1 < nblk) ? T.self - (2 * nblk - 1) * G2G_FSTRIDE : -1;
-                flags[T.self] = 0;
-                const int k = ti + tj;
-                if ((int) q[var].size() <= k) q[var].resize(k + 1);
-                q[var][k].push_back(T);
-            }
-        }
+        if (d.kind < 0) continue;
+        if (d.v2_ok) { i2[b->n2++] = i; if (d.v2_ok == 1) b->lds2 = std::max(b->lds2, v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, b->v2_threads)); }
+        else i1[b->n1++] = i;
     }
-    std::vector<V2Tile> all;
-    for (int v = 0; v < G2G_NVAR; ++v) {
-        b->var_off[v] = (int) all.size();
-        all.insert(all.end(), pre[v].begin(), pre[v].end());
-        for (size_t k = 0; k < q[v].size(); ++k) all.insert(all.end(), q[v][k].begin(), q[v][k].end());
-    }
-    b->var_off[G2G_NVAR] = (int) all.size();
-    for (int v = 0; v < 6; ++v) b->v6lds[v] = v6_layout(v6rows[v], v6ca4[v], v6rs[v]);
-    {   // what the v6 launches of this batch were given, read back as option V6_RING_PLAN (g2g_get_option): per launch that has
-        // strips "<class x 2 + Noll 3>:<S of the s ring>,<S of the t ring>,<T>,<LDS bytes>", joined by ';' (empty: no v6 launch)
-        std::string plan;
-        for (int s = 0; s < G2G_NVAR; ++s) {
-            const int v = variant_v6_index(s);
-            if (v < 0 || b->var_off[s + 1] == b->var_off[s]) continue;
-            char buf[96];
-            snprintf(buf, sizeof buf, "%s%d:%d,%d,%d,%d", plan.empty() ? "" : ";", v, b->v6lds[v].rs[0], b->v6lds[v].rs[1], b->v6lds[v].rtail, b->v6lds[v].total);
-            plan += buf;
-        }
-        ctx->opt["V6_RING_PLAN"] = std::make_pair(true, plan);
-    }
-    for (int v = 0; v < 8; ++v) b->v3lds[v] = v3_layout(need[v].rows_bytes, need[v].ca4, need[v].apool, need[v].bpool, b->v3_cols);
-    // test hook: G2G_INJECT_STALL=<i> makes the first strip / tile of problem i depend on a flag nobody ever writes
-    if (const char *e = g2g_opt(ctx, "INJECT_STALL")) {
-        const int victim = atoi(e);
-        const int never = (int) flags.size();
-        flags.resize(flags.size() + G2G_FSTRIDE, 0);
-        for (size_t k = 0; k < all.size(); ++k)
-            if (all[k].prob == victim && all[k].ti >= 0) { all[k].dep_up = never; break; }
-    }
-    b->fail_off = (int) flags.size();                 // per-DP fail flags behind the tile flags
-    flags.resize(flags.size() + (size_t) (n > 0 ? n : 1), 0);
-    b->dump_off = (int) flags.size();                 // the first time-out's view of its whole DP (g2g_wait_ge: G2G_DUMP_STRIPS strips x 7 words)
-    flags.resize(flags.size() + 2 + G2G_DUMP_WORDS * G2G_DUMP_STRIPS, 0);
-    b->xq_off = (int) flags.size();                   // queue heads of the bonus-aware variants
-    flags.resize(flags.size() + (G2G_NVAR - G2G_HDR), 0);
-    b->ntiles = (long long) all.size();
-    b->nflags = (int) flags.size();
-    b->flags0 = flags;
-    if (!all.empty()) {
-        hipError_t e2 = hipSuccess;
-        b->d_tiles = (V2Tile *) pool_take(ctx, sizeof(V2Tile) * all.size() + sizeof(int) * (ip.size() + 1), &b->tiles_cap);
-        if (!b->d_tiles) e2 = hipErrorOutOfMemory;
-        if (e2 == hipSuccess) e2 = hipMemcpy(b->d_tiles, all.data(), sizeof(V2Tile) * all.size(), hipMemcpyHostToDevice);
-        b->d_idxp = (int *) (b->d_tiles + all.size()); b->np = (int) ip.size();
-        if (e2 == hipSuccess && b->np) e2 = hipMemcpy(b->d_idxp, ip.data(), sizeof(int) * ip.size(), hipMemcpyHostToDevice);
-        if (e2 == hipSuccess) { b->d_flags = (int *) pool_take(ctx, sizeof(int) * flags.size(), &b->flags_cap); if (!b->d_flags) e2 = hipErrorOutOfMemory; }
-        if (e2 == hipSuccess) e2 = hipMemcpy(b->d_flags, flags.data(), sizeof(int) * flags.size(), hipMemcpyHostToDevice);
-        if (e2 != hipSuccess) { g2g_set_error("tiles: %s", hipGetErrorString(e2)); (void) hipGetLastError(); g2g_batch_free(b); return G2G_ERR_NOMEM; }
-    }
+}
+
+// 8. a queue plan becomes the batch's: two pool blocks (tiles + prologue list, flags), three copies, and option V6_RING_PLAN,
+// which reads back what the v6 launches of the batch were given (g2g_get_option)
+// (g2g_batch_free has taken the batch when this fails)
+static int upload_queues(g2g_ctx *ctx, g2g_batch *b, const QueuePlan &Q)
+{
+    if (Q.bad >= 0) { g2g_set_error("%s", "g2g_batch_prepare: a DP was given a kernel that has no variant slot"); g2g_batch_free(b); return G2G_ERR_DEVICE; }
+    memcpy(b->var_off, Q.var_off, sizeof b->var_off); memcpy(b->var_cells, Q.var_cells, sizeof b->var_cells);
+    memcpy(b->v3lds, Q.v3lds, sizeof b->v3lds); memcpy(b->v6lds, Q.v6lds, sizeof b->v6lds);
+    b->lds2p = Q.lds2p; b->simtile_lds = Q.simtile_lds; b->v2_maxrows = Q.v2_maxrows; b->v2_maxcols = Q.v2_maxcols;
+    b->fail_off = Q.fail_off; b->dump_off = Q.dump_off; b->xq_off = Q.xq_off;
+    b->ntiles = (long long) Q.tiles.size(); b->nflags = (int) Q.flags.size(); b->flags0 = Q.flags; b->np = 0;
+    ctx->opt["V6_RING_PLAN"] = std::make_pair(true, Q.v6_ring_plan);
+    if (Q.tiles.empty()) return G2G_OK;
+    const std::vector<V2Tile> &all = Q.tiles;
+    hipError_t e2 = hipSuccess;
+    b->d_tiles = (V2Tile *) pool_take(ctx, sizeof(V2Tile) * all.size() + sizeof(int) * (Q.ip.size() + 1), &b->tiles_cap);
+    if (!b->d_tiles) e2 = hipErrorOutOfMemory;
+    if (e2 == hipSuccess) e2 = hipMemcpy(b->d_tiles, all.data(), sizeof(V2Tile) * all.size(), hipMemcpyHostToDevice);
+    b->d_idxp = (int *) (b->d_tiles + all.size()); b->np = (int) Q.ip.size();
+    if (e2 == hipSuccess && b->np) e2 = hipMemcpy(b->d_idxp, Q.ip.data(), sizeof(int) * Q.ip.size(), hipMemcpyHostToDevice);
+    if (e2 == hipSuccess) { b->d_flags = (int *) pool_take(ctx, sizeof(int) * Q.flags.size(), &b->flags_cap); if (!b->d_flags) e2 = hipErrorOutOfMemory; }
+    if (e2 == hipSuccess) e2 = hipMemcpy(b->d_flags, Q.flags.data(), sizeof(int) * Q.flags.size(), hipMemcpyHostToDevice);
+    if (e2 != hipSuccess) { g2g_set_error("tiles: %s", hipGetErrorString(e2)); (void) hipGetLastError(); g2g_batch_free(b); return G2G_ERR_NOMEM; }
     return G2G_OK;
 }
 
@@ -900,255 +886,54 @@ static int batch_prepare_impl(g2g_ctx *ctx, int n, const g2g_problem *const *pro
         fprintf(stderr, "[g2g prepare] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - prep_t0).count());
         prep_t0 = t;
     };
-    g2g_batch *b = new g2g_batch();
-    b->ctx = ctx; b->n = n; b->d_arena = 0; b->d_probs = 0; b->fwd_ms = b->tb_ms = 0;
-    for (int k = 0; k < G2G_NVAR; ++k) { b->simscr[k] = 0; b->simscr_cap[k] = 0; }
-    for (int k = 0; k < 6; ++k) { b->twin[k] = 0; b->twin_cap[k] = 0; }
-    b->src.assign(prob, prob + n); b->fail_off = 0; b->dump_off = 0; b->force_v1 = force_v1; b->is_retry = false; b->n_recovered = 0;
-    b->recovered.assign(n, g2g_result()); b->was_recovered.assign(n, 0); b->ib.assign(n, 0); b->path_rec.assign(n, 0); b->xq_off = 0;
-    b->nsimmat = 0; b->injected = g2g_opt(ctx, "INJECT_STALL") != 0;
-    for (int k = 0; k < G2G_NVAR; ++k) b->var_cells[k] = 0;
-    b->last_timeouts = b->last_recovered = 0;
-    b->v3_cols = 128; b->v2_cols = G2G_V2_TILE_COLS;
-
-    b->dp.resize(n); b->status.assign(n, G2G_OK); b->cells.assign(n, 0); b->out_off.assign(n, 0); b->tcap.assign(n, 0); b->rr1.assign(n, 0);
+    const PrepOptions opts = prep_options(ctx);
+    g2g_batch *b = new_batch(ctx, n, prob, force_v1, opts);
+    const size_t n1 = (size_t) (n > 0 ? n : 1);
     Blob bl(ctx);
     if (const char *e = g2g_opt(ctx, "PACK_THREADS")) bl.pack_threads = atoi(e);
-    {   // size the staging buffer once (growing a pinned buffer means allocating and copying it again)
-        auto side_bytes = [&](const g2g_side &s) {
-            const size_t cols = (size_t) s.len + 2;
-            const g2g_side_dev *tw = (s.dev && s.dev->ctx == ctx) ? s.dev : 0;
-            size_t t = 8 * (size_t) s.many + 24 * cols + 256;
-            if (!(tw && tw->seq)) t += cols * s.many;
-            if (s.pseq && s.nelm > 0 && !(tw && tw->pseq)) t += 8 * cols * s.nelm;
-            if (s.has_gfq) for (int v = 0; v < 3; ++v) if (s.gfq.off[v] && !(tw && tw->freq[v])) t += 4 * cols + 12 * (size_t) s.gfq.off[v][s.len + 1] + 64;
-            if (s.gapdens) t += 16 * cols * s.many;
-            return t;
-        };
-        size_t est = (sizeof(DevProb) + 8) * (size_t) (n > 0 ? n : 1) + 4096;
-        for (int i = 0; i < n; ++i) {
-            const g2g_problem *p = prob[i];
-            if (check_problem(p) != G2G_OK) continue;
-            est += side_bytes(p->a) + side_bytes(p->b) + 8 * (size_t) (p->simmtx ? p->simdim * p->simrows : 0) + 64;
-        }
-        bl.grow(est);
-    }
-    size_t probs_off = bl.put(0, 0);
-    bl.extend(probs_off + sizeof(DevProb) * (size_t) (n > 0 ? n : 1));
+    bl.grow(staging_estimate(ctx, n, prob));
+    const size_t probs_off = bl.put(0, 0);
+    bl.extend(probs_off + sizeof(DevProb) * n1);
     std::vector<DevPatch> patches;            // descriptor fields that point at device-resident inputs (b->dp is never resized)
-    // 1. inputs
+    std::vector<DpFacts> facts(n);
     for (int i = 0; i < n; ++i) {
-        DevProb &d = b->dp[i];
-        memset(&d, 0, sizeof d);
-        const g2g_problem *p = prob[i];
-        int rc = check_problem(p);
-        b->status[i] = rc;
-        if (rc) { d.kind = -1; continue; }
-        d.kind = kind_of(p->alnmode);
-        d.noll = p->noll; d.sim2_kind = p->sim2_kind; d.crg2_kind = p->crg2_kind; d.codonk1 = p->codonk1;
-        d.rect = is_rect(p->alnmode) ? 1 : 0;
-        d.lw = p->lw; d.up = p->up;
-        if (d.rect) { d.lw = p->b.left - p->a.right; d.up = p->b.right - p->a.left; }     // every cell and every boundary corner inside
-        d.width = d.up - d.lw + 3;
-        d.basic_gop = p->basic_gop; d.weighted_gop = p->weighted_gop; d.u = p->u;
-        d.u2divu1 = p->u2divu1; d.v2divv1 = p->v2divv1;
-        d.simdim = p->simdim;
-        if (p->simmtx) d.simmtx = OFF<const double>(bl.put(p->simmtx, sizeof(double) * (size_t) p->simdim * p->simrows));
-        pack_side(bl, p->a, d.a, d.kind, d.kind == 1 || d.kind == 2, patches);
-        pack_side(bl, p->b, d.b, d.kind, d.kind == 2, patches);
-        d.spb_fact = p->spb_fact; d.dvsp = p->dvsp;
-        {
-            std::vector<BonusCell> bc;
-            intron_bonus_table(p, bc);
-            if (!bc.empty()) {
-                std::vector<int> bm, bn; std::vector<double> bh, bx;
-                for (const BonusCell &c : bc) { bm.push_back(c.m); bn.push_back(c.n); bh.push_back(c.h); bx.push_back(c.mx); }
-                d.nbonus = (int) bc.size();
-                // the per-row index of the strip kernels behind bon_m's entries: first entry of row a.left + r, r = 0 .. rows
-                // (the table is row-major with n ascending within a row; g2g_forward_kernel reads the first nbonus entries only)
-                {
-                    const int rows = p->a.right - p->a.left;
-                    size_t k = 0;
-                    for (int r = 0; r <= rows; ++r) {
-                        while (k < bc.size() && bc[k].m < p->a.left + r) ++k;
-                        bm.push_back((int) k);
-                    }
-                }
-                // (put_now: the four vectors are gone by the time flush() makes put()'s deferred copies)
-                d.bon_m = OFF<const int>(bl.put_now(bm.data(), sizeof(int) * bm.size()));
-                d.bon_n = OFF<const int>(bl.put_now(bn.data(), sizeof(int) * bn.size()));
-                d.bon_h = OFF<const double>(bl.put_now(bh.data(), sizeof(double) * bh.size()));
-                d.bon_mx = OFF<const double>(bl.put_now(bx.data(), sizeof(double) * bx.size()));
-            }
-        }
+        b->status[i] = pack_problem(bl, prob[i], b->dp[i], patches);
+        facts[i] = dp_facts(b->dp[i], prob[i]);
     }
-    // Tile widths.  Tiles of one DP run as a wavefront, at most min(strips, blocks) of them at a time: a sweep with
-    // hundreds of DPs fills the GPU with wide tiles (few block-boundary records, short fill/drain share), a rank
-    // that holds few DPs (the 8-GPU shard) needs narrow ones or its waves sit idle behind the dependencies.
-    {
-        const int ncu = ctx->ncu;
-        auto pick = [&](int kind, int R, int cmax, int cmin, int slots) {
-            int C = cmax;
-            for (; C > cmin; C /= 2) {
-                long long par = 0;
-                for (int i = 0; i < n; ++i) {
-                    const DevProb &d = b->dp[i];
-                    if (d.kind != kind) continue;
-                    const int ns = (d.a.right - d.a.left + R - 1) / R, nb = (d.b.right - d.b.left + C - 1) / C;
-                    par += std::min(ns, nb);
-                }
-                if (4 * par >= 5 * (long long) slots) break;
-            }
-            return C;
-        };
-        b->v3_cols = pick(1, 64, 128, 32, ncu * 4);
-        // v2 (_pf): 16-row strips in 2-wave workgroups when the batch offers enough tiles (less barrier idling, 7 % faster
-        // on a full sweep), 32-row strips otherwise (half as many strips on a DP's critical path)
-        b->v2_threads = 128;
-        if (pick(2, 16, 128, 64, ncu * 6) != 128) b->v2_threads = 256;      // (measured crossover: between 1/4 and 1/8 of the bench sweep)
-        if (const char *e = g2g_opt(ctx, "V2_THREADS")) { const int t = atoi(e); if (t == 128 || t == 256) b->v2_threads = t; }
-        b->v2_cols = pick(2, b->v2_threads / 8, G2G_V2_TILE_COLS, 64, ncu * (768 / b->v2_threads));
-        if (const char *e = g2g_opt(ctx, "V2_COLS")) { const int c = atoi(e); if (c >= 16 && c <= 4096) b->v2_cols = c; }
-        if (const char *e = g2g_opt(ctx, "V3_COLS")) { const int c = atoi(e); if (c >= 16 && c <= 4096) b->v3_cols = c; }
-        // v6 or v2 for the _pf DPs of this batch?  v6 has the higher throughput (a full sweep: 750 vs 800 ms) but the longer critical
-        // path per DP (64-row strips at one wave per SIMD, ~19 us per step): a batch that cannot fill the machine -- a rank's share of
-        // a sharded sweep -- finishes sooner on v2's 16-row strips.  Measured on shares of the bench sweep (v6 / v2, ms): 1/2 436 / 456,
-        // 1/3 405 / 311, 1/4 327 / 254, 1/8 283 / 163.  Threshold: 35 strips of 64 rows per CU (between the 1/2 and the 1/3 share).
-        {
-            long long s6 = 0;
-            for (int i = 0; i < n; ++i) if (b->dp[i].kind == 2) s6 += (b->dp[i].a.right - b->dp[i].a.left + 63) / 64;
-            long long min_strips = 35LL * ncu;
-            if (const char *e = g2g_opt(ctx, "V6_MIN_STRIPS")) min_strips = atoll(e);
-            b->v6_on = s6 >= min_strips;
-        }
-        b->v3_sweep = g2g_opt(ctx, "V3_SWEEP") ? atoi(g2g_opt(ctx, "V3_SWEEP")) : 1;
-        b->v2_sweep = g2g_opt(ctx, "V2_SWEEP") ? atoi(g2g_opt(ctx, "V2_SWEEP")) : 1;
+    const BatchShape shape = batch_shape(facts.data(), n, opts);
+    b->v3_cols = shape.v3_cols; b->v2_threads = shape.v2_threads; b->v2_cols = shape.v2_cols; b->v6_on = shape.v6_on;
+    b->v3_sweep = shape.v3_sweep; b->v2_sweep = shape.v2_sweep;
+    std::vector<KernelChoice> choice(n);
+    for (int i = 0; i < n; ++i) {
+        if (b->dp[i].kind < 0) { const KernelChoice none = {0, 0, 0, {{0, 0, 0}, 0, {0, 0, 0}}}; choice[i] = none; continue; }
+        choice[i] = choose_kernel(facts[i], shape, opts, force_v1);
+        b->dp[i].v2_ok = choice[i].generation; b->ib[i] = choice[i].ib;
     }
-    // index lists for the two forward kernels (filled below, once eligibility is known)
+    // index lists for the two forward kernels (filled below, once the arena has its address)
     const size_t idx_off = bl.put(0, 0);
-    bl.extend(idx_off + sizeof(int) * 2 * (size_t) (n > 0 ? n : 1));
+    bl.extend(idx_off + sizeof(int) * 2 * n1);
     b->in_bytes = (bl.size() + 255) & ~(size_t) 255;
-    // 2. state / trace / outputs (device only)
-    size_t off = b->in_bytes;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 15) & ~(size_t) 15; return o; };
-    for (int i = 0; i < n; ++i) {
-        DevProb &d = b->dp[i];
-        if (d.kind < 0) continue;
-        const g2g_problem *p = prob[i];
-        const size_t W = d.width;
-        if (d.kind == 1) { d.capa = p->a.gfq.hetero + 1; d.capb = 0; }
-        else if (d.kind == 2) { d.capa = p->a.gfq.hetero + 1; d.capb = p->b.gfq.hetero + 1; }
-        else if (d.kind == 3) { d.capa = p->a.many; d.capb = p->b.many; }
-        auto v1_state = [&]() {                // the diagonal-indexed row buffers of g2g_forward_kernel (v1): only for DPs it runs
-            for (int x = 0; x < NX; ++x) {
-                if (d.noll != 3 && (x == XG2 || x == XF2)) continue;
-                d.val[x] = OFF<double>(take(sizeof(double) * W));
-                d.dir[x] = OFF<uint8_t>(take(W));
-                if (d.kind == 1 || d.kind == 2) d.dla[x] = OFF<int2>(take(sizeof(int2) * W * d.capa));
-                if (d.kind == 2) d.dlb[x] = OFF<int2>(take(sizeof(int2) * W * d.capb));
-                if (d.kind == 1) d.glb[x] = OFF<int>(take(sizeof(int) * W));
-                if (d.kind == 3) d.glb[x] = OFF<int>(take(sizeof(int) * W * (d.capa + d.capb)));
-            }
-            d.spw = (int) W;
-        };
-        // anti-diagonal extent and the widest anti-diagonal
-        const int al = p->a.left, ar = p->a.right, bl_ = p->b.left, br = p->b.right;
-        d.d0 = al + bl_; d.d1 = (ar - 1) + (br - 1);
-        int tmax = 1;
-        long long cells = 0;
-        for (int dd = d.d0; dd <= d.d1; ++dd) {
-            int mlo, mhi;
-            diag_rows(dd, al, ar, bl_, br, d.lw, d.up, &mlo, &mhi);
-            int c = mhi - mlo + 1;
-            if (c > 0) cells += c;
-            if (c > tmax) tmax = c;
-        }
-        b->cells[i] = cells; d.cells = cells;
-        d.tstride = tmax;
-        d.trace = OFF<uint8_t>(take((size_t) (d.d1 - d.d0 + 1) * tmax));
-        d.v2_ok = choose_kernel(ctx, b, d, p, force_v1, &b->ib[i]);
-        if (!d.v2_ok) v1_state();
-        else {                                  // g2g_spscore_kernel keeps its two dynamic lists in dla/dlb[XH] (stride spw)
-            d.spw = 1;
-            d.dla[XH] = OFF<int2>(take(sizeof(int2) * (size_t) (d.capa + 1)));
-            if (d.kind == 2) d.dlb[XH] = OFF<int2>(take(sizeof(int2) * (size_t) (d.capb + 1)));
-        }
-        if (d.v2_ok) {
-            const size_t recsz = d.v2_ok == 8 ? 4 * V8_REC : (16 + 4 * (size_t) (d.capa + (d.kind == 2 ? d.capb : 0)) + 15) & ~(size_t) 15;
-            d.v2_rowstride = p->b.len + 3;
-            d.v2_rowH = OFF<void>(take(3 * recsz * (size_t) d.v2_rowstride));
-            d.v2_rowG = OFF<void>(take(3 * recsz * (size_t) d.v2_rowstride));
-            if (d.noll == 3) d.v2_rowG2 = OFF<void>(take(3 * recsz * (size_t) d.v2_rowstride));
-            d.v2_colH = OFF<void>(take(recsz * ((size_t) (ar - al) + 3)));
-            d.v2_cbH = OFF<void>(take(recsz * ((size_t) (ar - al) + 3)));
-            d.v2_cbF = OFF<void>(take(recsz * ((size_t) (ar - al) + 3)));
-            if (d.noll == 3) d.v2_cbF2 = OFF<void>(take(recsz * ((size_t) (ar - al) + 3)));
-            d.v2_rowoff = OFF<long long>(take(sizeof(long long) * ((size_t) (ar - al) + 2)));
-            // the column-score matrix: only for DPs whose kernel reads one (strips in sweep mode make their own, block by block)
-            const bool own_sim = !g2g_opt(ctx, "NO_SIMBLK") && (d.v2_ok >= 6 || (d.v2_ok == 1 && b->v2_sweep) || ((d.v2_ok == 2 || d.v2_ok == 3) && d.kind == 1 && b->v3_sweep));
-            if (!own_sim) { d.v2_sim = OFF<double>(take(sizeof(double) * (size_t) cells + 64)); ++b->nsimmat; }
-        }
-        b->rr1[i] = (long long) (bl_ - al) + (br - ar);
-        d.tcap = (ar - al) + (br - bl_) + 4;
-        b->tcap[i] = d.tcap;
-    }
-    // outputs of all problems in ONE contiguous region (a single device-to-host copy fetches a whole sweep)
-    b->out_lo = off;
-    for (int i = 0; i < n; ++i) {
-        DevProb &d = b->dp[i];
-        if (d.kind < 0) continue;
-        b->out_off[i] = take(sizeof(double) + sizeof(int) * 2 + sizeof(int2) * (size_t) d.tcap);
-        d.score = OFF<double>(b->out_off[i]);
-        d.ntrace = OFF<int>(b->out_off[i] + sizeof(double));
-        d.otrace = OFF<int2>(b->out_off[i] + sizeof(double) + 2 * sizeof(int));
-    }
-    b->out_hi = off;
-    b->arena_bytes = off + 256;
+    layout_arena(b, shape, opts);
     bl.flush();
     if (bl.oom) { g2g_set_error("%s", "host staging buffer: out of (pinned) memory"); delete b; return G2G_ERR_NOMEM; }
     prep_lap("host image of the inputs");
-    hipError_t e = hipSuccess;
     b->d_arena = (char *) pool_take(ctx, b->arena_bytes, &b->arena_cap);
-    if (!b->d_arena) e = hipErrorOutOfMemory;
     prep_lap("hipMalloc(arena)");
-    if (e != hipSuccess) {
-        g2g_set_error("hipMalloc(arena): %s", hipGetErrorString(e));
+    if (!b->d_arena) {
+        g2g_set_error("hipMalloc(arena): %s", hipGetErrorString(hipErrorOutOfMemory));
         (void) hipGetLastError();              // a failed allocation must not poison the next launch check of this thread
         delete b; return G2G_ERR_NOMEM;
     }
-    for (int i = 0; i < n; ++i) {
-        DevProb &d = b->dp[i];
-        if (d.kind < 0) continue;
-        rebase(d.simmtx, b->d_arena);
-        rebase(d.bon_m, b->d_arena); rebase(d.bon_n, b->d_arena); rebase(d.bon_h, b->d_arena); rebase(d.bon_mx, b->d_arena);
-        rebase_side(d.a, b->d_arena); rebase_side(d.b, b->d_arena);
-        for (int x = 0; x < NX; ++x) {
-            rebase(d.val[x], b->d_arena); rebase(d.dir[x], b->d_arena); rebase(d.dla[x], b->d_arena);
-            rebase(d.dlb[x], b->d_arena); rebase(d.glb[x], b->d_arena);
-        }
-        rebase(d.v2_rowH, b->d_arena); rebase(d.v2_rowG, b->d_arena); rebase(d.v2_rowG2, b->d_arena); rebase(d.v2_colH, b->d_arena);
-        rebase(d.v2_cbH, b->d_arena); rebase(d.v2_cbF, b->d_arena); rebase(d.v2_cbF2, b->d_arena);
-        rebase(d.v2_rowoff, b->d_arena); rebase(d.v2_sim, b->d_arena);
-        rebase(d.trace, b->d_arena); rebase(d.score, b->d_arena); rebase(d.ntrace, b->d_arena); rebase(d.otrace, b->d_arena);
-    }
+    for (int i = 0; i < n; ++i) if (b->dp[i].kind >= 0) rebase_problem(b->dp[i], b->d_arena);
     for (const DevPatch &pt : patches) *pt.field = pt.value;
-    {
-        int *i1 = (int *) (bl.data() + idx_off), *i2 = i1 + (n > 0 ? n : 1);
-        b->n1 = b->n2 = 0; b->lds2 = 0;
-        for (int i = 0; i < n; ++i) {
-            const DevProb &d = b->dp[i];
-            if (d.kind < 0) continue;
-            if (d.v2_ok) { i2[b->n2++] = i; if (d.v2_ok == 1) b->lds2 = std::max(b->lds2, v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, b->v2_threads)); }
-            else i1[b->n1++] = i;
-        }
-        b->d_idx1 = (int *) (b->d_arena + idx_off);
-        b->d_idx2 = b->d_idx1 + (n > 0 ? n : 1);
-    }
-    if (int rc = build_queues(ctx, b, prob)) return rc;
+    fill_index_lists(b, (int *) (bl.data() + idx_off), (int *) (bl.data() + idx_off) + n1);
+    b->d_idx1 = (int *) (b->d_arena + idx_off);
+    b->d_idx2 = b->d_idx1 + n1;
+    if (int rc = upload_queues(ctx, b, queue_plan(facts.data(), choice.data(), b->cells.data(), shape, opts, n))) return rc;
     prep_lap("descriptors, tiles, flags");
     if (n) memcpy(bl.data() + probs_off, b->dp.data(), sizeof(DevProb) * (size_t) n);
     b->d_probs = (DevProb *) (b->d_arena + probs_off);
-    e = hipMemcpyAsync(b->d_arena, bl.data(), bl.size(), hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(b->d_arena, bl.data(), bl.size(), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { g2g_set_error("upload: %s", hipGetErrorString(e)); g2g_batch_free(b); return G2G_ERR_DEVICE; }
     prep_lap("upload");
@@ -1860,15 +1645,9 @@ static size_t problem_bytes(const g2g_ctx *ctx, const g2g_problem *p)
 {
     if (check_problem(p)) return 4096;
     const int al = p->a.left, ar = p->a.right, bl = p->b.left, br = p->b.right;
-    long long cells = 0;
-    int tmax = 1;
-    for (int dd = al + bl; dd <= (ar - 1) + (br - 1); ++dd) {
-        int mlo, mhi;
-        diag_rows(dd, al, ar, bl, br, is_rect(p->alnmode) ? bl - ar : p->lw, is_rect(p->alnmode) ? br - al : p->up, &mlo, &mhi);
-        const int c = mhi - mlo + 1;
-        if (c > 0) cells += c;
-        if (c > tmax) tmax = c;
-    }
+    const BandCells bc = band_cells(al, ar, bl, br, is_rect(p->alnmode) ? bl - ar : p->lw, is_rect(p->alnmode) ? br - al : p->up);
+    const long long cells = bc.cells;
+    const int tmax = bc.tstride;
     // trace (1 B per cell) + the column-score matrix (8 B per cell) where a kernel reads one: strips in sweep mode (the
     // default of every tiled kernel) make their own scores
     const bool matrix = g2g_opt(ctx, "NO_SIMBLK") || g2g_opt(ctx, "V2_SWEEP") || g2g_opt(ctx, "V3_SWEEP");   // (tile-mode test configurations)

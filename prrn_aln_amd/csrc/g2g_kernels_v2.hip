@@ -1107,7 +1107,6 @@ g2g_v2_prologue_kernel(const DevProb *probs, const int *idx, int pro_off)
 extern "C" __global__ void g2g_v2_prologue_kernel(const DevProb *probs, const int *idx, int pro_off);
 #endif
 
-__host__ __device__ __forceinline__ bool sim_tiled_kind(int k) { return k == 31 || k == 320 || k == 321 || k == 33 || k == 330; }
 // PwdM::sim2 for every in-band cell of the gap-profile DPs (maln.h:160-172, maln2.cc:534-623,1230-1296):
 // independent of the recurrence, so it is computed ahead of it, fully parallel, row-major per DP
 #ifdef G2G_TU_V2
@@ -1133,8 +1132,6 @@ extern "C" __global__ void g2g_v2_sim_kernel(const DevProb *probs, const int *id
 // and the 128 columns of b (residues or frequency vectors) in LDS once and computes 4096 scores from there.  The
 // row-by-row kernel above re-reads b's column data for every row: 1.6e9 cells x 184 B through L2 for sim33, which is
 // what made it take 34 ms per sweep.  Expressions and summation order are those of sim2() (g2g_kernels.hip).
-#define SIM_TR 64
-#define SIM_TC 128
 // sim33 / sim33_n rows of one thread's column: b's frequency vector sits in registers (NB: compile-time bound of felm),
 // a's profile row is a wave-uniform LDS read.  Same products, same summation order as sim2().
 template <int NB, bool DC>
@@ -1207,9 +1204,6 @@ g2g_v2_sim_tile_kernel(const DevProb *probs, const int *idx)
 #else
 extern "C" __global__ void g2g_v2_sim_tile_kernel(const DevProb *probs, const int *idx);
 #endif
-
-// self / dep_*: indices into the batch's tile-completion flags (-1: no such neighbour)
-struct V2Tile { int prob, ti, tj, nsteps, self, dep_up, dep_left, dep_diag, dep_war; };
 
 // One PERSISTENT kernel per (record type, Noll) -- the register budget of a combined kernel would be its
 // worst variant's.  Workgroups pull tiles from a queue ordered by tile wavefront (i + j) and wait on

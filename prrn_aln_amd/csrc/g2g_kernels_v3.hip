@@ -23,10 +23,7 @@
 // fence only.
 #include <hip/hip_runtime.h>
 
-// byte offsets of the LDS regions of a v3 launch (host: v3_lds_plan)
-struct V3Lds { int rows, black, stsc, aglen, afreq, boff, bglen, bfreq, svals, sink, total; };
-
-#include "g2g_lds.h"                // v3_pitch: dwords per LDS row of dynamic lists (shared with the host's plans)
+#include "g2g_lds.h"                // V3Lds, G2G_V3_NA, v3_pitch: dwords per LDS row of dynamic lists (shared with the host's plans)
 
 
 
@@ -857,9 +854,6 @@ V3_SIG(NAME, __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
 }
 #ifndef G2G_V3R_WPE
 #define G2G_V3R_WPE 2
-#endif
-#ifndef G2G_V3_NA
-#define G2G_V3_NA 16                 // register-resident static lists: up to this many entries (incl. terminator)
 #endif
 #ifdef G2G_TU_V3
 V3_KERNEL(g2g_v3_hf2, 1, false, 0, 2)

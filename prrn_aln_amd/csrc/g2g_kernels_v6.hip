@@ -869,12 +869,6 @@ V6_SIG(NAME, __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
         __syncthreads();                                                                            \
     }                                                                                               \
 }
-#ifndef G2G_V6_NA
-#define G2G_V6_NA 16
-#endif
-#ifndef G2G_V6_NA3
-#define G2G_V6_NA3 10                   /* Noll 3: two more records per cell -- with 16-entry row lists the kernel would spill 94 registers */
-#endif
 #ifdef G2G_TU_V6
 V6_KERNEL(g2g_v6_pf2, false, G2G_V6_NA, 1)
 V6_KERNEL(g2g_v6_pf3, true, G2G_V6_NA3, 1)

@@ -15,7 +15,6 @@
 // v1 ran these DPs with one workgroup per DP and every record and every length in HBM.
 #include <hip/hip_runtime.h>
 
-#define V8_REC 12                                            // dwords of a record in HBM / in the staging slots
 struct NL { int g[6]; };
 __device__ __forceinline__ NL nl_zero() { NL r; _Pragma("unroll") for (int k = 0; k < 6; ++k) r.g[k] = 0; return r; }
 __device__ __forceinline__ NL nl_up(const NL &x) { NL r; _Pragma("unroll") for (int k = 0; k < 6; ++k) r.g[k] = dpp_up1(x.g[k]); return r; }

@@ -38,4 +38,34 @@ struct V6Lds { int rows, black, stsc, svals, sink, total; int ringk[3], ringf[3]
 #define V6_RHCOLS 128                   // columns of the per-column array of r-list heads (a power of 2 >= V6_WINDOW)
 static_assert(V6_AHEAD >= V6_FEED - 1 && V6_RHCOLS >= V6_WINDOW && (V6_RHCOLS & (V6_RHCOLS - 1)) == 0, "v6 ring windows");
 
+// byte offsets of the LDS regions of a v3 launch (host: v3_layout of g2g_plan.h)
+struct V3Lds { int rows, black, stsc, aglen, afreq, boff, bglen, bfreq, svals, sink, total; };
+
+// A queue entry of a persistent kernel: tile (ti, tj) of DP prob (ti -1 / -2: its top / left boundary chain), nsteps steps;
+// self / dep_*: indices into the batch's tile-completion flags (-1: no such neighbour)
+struct V2Tile { int prob, ti, tj, nsteps, self, dep_up, dep_left, dep_diag, dep_war; };
+
+// Longest static list (terminator included) a kernel keeps in registers: what the host's kernel choice tests
+#ifndef G2G_V3_NA
+#define G2G_V3_NA 16                    // v3r
+#endif
+#ifndef G2G_V6_NA
+#define G2G_V6_NA 16
+#endif
+#ifndef G2G_V6_NA3
+#define G2G_V6_NA3 10                   /* Noll 3: two more records per cell -- with 16-entry row lists the kernel would spill 94 registers */
+#endif
+#define V8_REC 12                       // v8: dwords of a record in HBM / in the staging slots
+
+// the tiled column-score kernel (g2g_v2_sim_tile_kernel): rows x columns of a block, and the scorers it knows
+#define SIM_TR 64
+#define SIM_TC 128
+G2G_HD inline bool sim_tiled_kind(int k) { return k == 31 || k == 320 || k == 321 || k == 33 || k == 330; }
+
+// d_flags (g2g_strip.h says what lives where and why)
+#define G2G_FSTRIDE 64                  // ints between two tile flags / progress words
+#define G2G_DUMP_STRIPS 580             // strips of one DP the first time-out dumps for the host ...
+#define G2G_DUMP_WORDS 11               // ... words each: progress word, HW_ID, three markers, two publish columns, (step, place) of two waves
+#define G2G_HDRN 104                    // header words: 4 + the snapshot (want, seen, offset of the polled word, the words at and below it; [48, 64): per-wave heartbeats); G2G_HDR + G2G_HDRN is a multiple of G2G_FSTRIDE, so every progress line IS one 128-byte line
+
 #endif

@@ -1,6 +1,8 @@
-// g2g_plan.h -- the host-side decisions of a batch run as plain values: which variant slot is which kernel, how the CUs are
-// shared out, the list of persistent launches, the text of a time-out report, and the LDS plan of the v6 launches.  Plain C++17 without HIP types (it
-// compiles with g++: tests/host/plan_main.cc and v6_layout_main.cc pin all of it without a GPU); g2g_engine.hip executes what is planned here.
+// g2g_plan.h -- the host-side decisions of a batch as plain values.  Of a run: which variant slot is which kernel, how the CUs are
+// shared out, the list of persistent launches, the text of a time-out report, and the LDS plan of the v6 launches.  Of prepare: the
+// shape of the batch (tile widths, strip heights, v6 or not), the kernel of each DP, and its queues (tiles, flag image, LDS plans).
+// Plain C++17 without HIP types (it compiles with g++: tests/host/plan_main.cc and v6_layout_main.cc pin all of it without a GPU);
+// g2g_engine.hip fills the facts and executes what is planned here.
 #ifndef G2G_PLAN_H
 #define G2G_PLAN_H
 #include <stdarg.h>
@@ -466,4 +468,352 @@ static inline int v6_rows_bytes(int capa, int capb, int noll)
 // included (37-40 KB now; the rest of the sweep: up to 35 KB).  Classes B (up to V6_SMALL_KB) and C (V6_LARGE_KB) stay as
 // options for measurements.
 static const int V6_CLASS_A = 40 * 1024;
+
+// ---- (f) prepare: what a batch's DPs are, the shape of the batch, the kernel of each DP ---------------------------------
+// Every option g2g_batch_prepare reads, read once (prep_options in g2g_engine.hip).
+struct PrepOptions {
+    int ncu;
+    bool force_v1, no_v7, no_v8, force_v2, no_v6, no_areg, no_strip_bonus, no_chainq, no_simblk;
+    int v6_small, v6_large;         // V6_SMALL_KB / V6_LARGE_KB in bytes: the limits of footprint classes B and C (40 KB and none when not set)
+    int v2_threads, v2_cols, v3_cols;           // V2_THREADS / V2_COLS / V3_COLS (0: not set)
+    bool min_strips_set; long long min_strips;  // V6_MIN_STRIPS
+    int v3_sweep, v2_sweep;         // V3_SWEEP / V2_SWEEP (1 when not set)
+    bool inject; int inject_victim; // INJECT_STALL (test hook)
+};
+static inline PrepOptions prep_defaults(int ncu)
+{
+    PrepOptions o = {ncu, false, false, false, false, false, false, false, false, false, 40 * 1024, 0, 0, 0, 0, false, 0, 1, 1, false, 0};
+    return o;
+}
+// What the decisions need of one DP (filled once per DP, after its sides were packed).
+struct SideFacts {
+    int len, many, left, right, nelm, felm;
+    int maxlist, r_from_t;          // DevSide's (0 for a side whose gap profiles the DP does not read)
+    bool gapdens, postgapdens, weight;          // the array is there
+    const int32_t *off[3];          // gfq.off of the three views
+};
+struct DpFacts {
+    int kind;                       // DevProb::kind (-1: not a valid problem)
+    int rect, noll, capa, capb, nbonus, crg2_kind, sim2_kind, lw, up;
+    SideFacts a, b;
+};
+struct BatchShape { int v3_cols, v2_threads, v2_cols; bool v6_on; int v3_sweep, v2_sweep; };
+#define G2G_PLAN_V2_TILE_COLS 512   // G2G_V2_TILE_COLS of the build flags (the engine asserts that they agree)
+
+// Tile widths.  Tiles of one DP run as a wavefront, at most min(strips, blocks) of them at a time: a sweep with
+// hundreds of DPs fills the GPU with wide tiles (few block-boundary records, short fill/drain share), a rank
+// that holds few DPs (the 8-GPU shard) needs narrow ones or its waves sit idle behind the dependencies.
+static inline BatchShape batch_shape(const DpFacts *facts, int n, const PrepOptions &o)
+{
+    BatchShape s;
+    const int ncu = o.ncu;
+    auto pick = [&](int kind, int R, int cmax, int cmin, int slots) {
+        int C = cmax;
+        for (; C > cmin; C /= 2) {
+            long long par = 0;
+            for (int i = 0; i < n; ++i) {
+                const DpFacts &d = facts[i];
+                if (d.kind != kind) continue;
+                const int ns = (d.a.right - d.a.left + R - 1) / R, nb = (d.b.right - d.b.left + C - 1) / C;
+                par += std::min(ns, nb);
+            }
+            if (4 * par >= 5 * (long long) slots) break;
+        }
+        return C;
+    };
+    s.v3_cols = pick(1, 64, 128, 32, ncu * 4);
+    // v2 (_pf): 16-row strips in 2-wave workgroups when the batch offers enough tiles (less barrier idling, 7 % faster
+    // on a full sweep), 32-row strips otherwise (half as many strips on a DP's critical path)
+    s.v2_threads = 128;
+    if (pick(2, 16, 128, 64, ncu * 6) != 128) s.v2_threads = 256;      // (measured crossover: between 1/4 and 1/8 of the bench sweep)
+    if (o.v2_threads == 128 || o.v2_threads == 256) s.v2_threads = o.v2_threads;
+    s.v2_cols = pick(2, s.v2_threads / 8, G2G_PLAN_V2_TILE_COLS, 64, ncu * (768 / s.v2_threads));
+    if (o.v2_cols >= 16 && o.v2_cols <= 4096) s.v2_cols = o.v2_cols;
+    if (o.v3_cols >= 16 && o.v3_cols <= 4096) s.v3_cols = o.v3_cols;
+    // v6 or v2 for the _pf DPs of this batch?  v6 has the higher throughput (a full sweep: 750 vs 800 ms) but the longer critical
+    // path per DP (64-row strips at one wave per SIMD, ~19 us per step): a batch that cannot fill the machine -- a rank's share of
+    // a sharded sweep -- finishes sooner on v2's 16-row strips.  Measured on shares of the bench sweep (v6 / v2, ms): 1/2 436 / 456,
+    // 1/3 405 / 311, 1/4 327 / 254, 1/8 283 / 163.  Threshold: 35 strips of 64 rows per CU (between the 1/2 and the 1/3 share).
+    long long s6 = 0;
+    for (int i = 0; i < n; ++i) if (facts[i].kind == 2) s6 += (facts[i].a.right - facts[i].a.left + 63) / 64;
+    s.v6_on = s6 >= (o.min_strips_set ? o.min_strips : 35LL * ncu);
+    s.v3_sweep = o.v3_sweep;
+    s.v2_sweep = o.v2_sweep;
+    return s;
+}
+
+// bytes of a strip-boundary record in HBM and in the staging slots: v8 fixed, else 16 + the dynamic lists' entries, in 16-byte units
+static inline size_t strip_record_bytes(int generation, int kind, int capa, int capb)
+{
+    return generation == G2G_V8 ? 4 * V8_REC : (16 + 4 * (size_t) (capa + (kind == 2 ? capb : 0)) + 15) & ~(size_t) 15;
+}
+// LDS footprint of the 8-lanes-per-cell strips (v2) for one problem (see V2Geom): (slots * R + extras) records
+static inline size_t v2_lds_bytes(int kind, int noll, int capa, int capb, int mla, int mlb, int threads)
+{
+    const size_t recsz = strip_record_bytes(G2G_V2, kind, capa, capb);
+    const size_t R = threads / 8;
+    const size_t lists = (size_t) 10 * 3 * (R * mla + (kind == 2 ? (R + 2) * mlb : 0)) + 8;   // glen i16 + freq f64
+    return (((noll == 3 ? 9 : 6) * R + 5) * recsz + 16 * R + lists + 16 + 15) & ~(size_t) 15;
+}
+// (v2 caches static gap lengths as SIGNED 16-bit with negative = terminator: a gap run can be as long as the group has columns,
+// so sides of 32768 columns or more are not eligible -- they stay on v3 / v1, which keep 32 bits)
+static inline bool v2_fits(const DpFacts &d, int threads)
+{
+    return std::max(d.a.len, d.b.len) < 32768 && v2_lds_bytes(d.kind, d.noll, d.capa, d.capb, d.a.maxlist, d.b.maxlist, threads) + 4 * threads <= V2_LDS_MAX;
+}
+// LDS plan of the v3 kernel (g2g_kernels_v3.hip) for one problem with C-column tiles: ring rows, the black
+// list, staging scalars, and the static-list pools of a strip's rows / a block's columns
+static inline V3Lds v3_layout(int rows_bytes, int ca4max, int apool, int bpool, int C)
+{
+    V3Lds L;
+    int o = 0;
+    auto take = [&](int bytes) { int r = o; o = (o + bytes + 15) & ~15; return r; };
+    L.rows = take(rows_bytes);
+    L.black = take(4 * (ca4max + 4));
+    L.stsc = take(4 * 28);
+    L.aglen = take(4 * (apool + 4));
+    L.afreq = take(8 * (apool + 4));
+    L.boff = take(bpool ? 4 * 3 * C : 0);
+    L.bglen = take(bpool ? 4 * (bpool + 4) : 0);
+    L.bfreq = take(bpool ? 8 * (bpool + 4) : 0);
+    L.svals = take(4 * 64);
+    L.sink = take(4 * 64);
+    L.total = o;
+    return L;
+}
+struct V3Need { int rows_bytes, ca4, apool, bpool, total; };
+static inline V3Need v3_need(const DpFacts &d, int C, bool areg = false)
+{
+    V3Need n;
+    const int capb = d.kind == 2 ? d.capb : 0;
+    n.ca4 = (d.capa + 3) & ~3;
+    const int lsz = n.ca4 + ((capb + 3) & ~3);
+    n.rows_bytes = 65 * v3_pitch(d.noll == 3 ? 9 : 6, lsz) * 4;
+    n.apool = 0; n.bpool = 0;
+    const int al = d.a.left, ar = d.a.right, bl = d.b.left, br = d.b.right;
+    for (int m0 = al; m0 < ar; m0 += 64) {
+        const int me = std::min(m0 + 64, ar);
+        int c = 0;
+        for (int v = 0; v < 3; ++v) c += d.a.off[v][me + 1] - d.a.off[v][m0 + 1];
+        n.apool = std::max(n.apool, c);
+    }
+    if (d.kind == 2)
+        for (int c0 = bl; c0 < br; c0 += C) {
+            const int c1 = std::min(c0 + C, br);
+            int c = 0;
+            for (int v = 0; v < 3; ++v) c += d.b.off[v][c1 + 1] - d.b.off[v][c0 + 1];
+            n.bpool = std::max(n.bpool, c);
+        }
+    if (d.kind == 2 && !n.bpool) n.bpool = 1;
+    if (areg) n.apool = 0;                                  // the rows' static lists live in registers
+    n.total = v3_layout(n.rows_bytes, n.ca4, n.apool, n.bpool, C).total;
+    return n;
+}
+
+// Which kernel generation runs a DP (DevProb::v2_ok): 0 g2g_forward_kernel, 1 v2, 2 v3 with LDS lists, 3 v3r, 6, 7, 8; ib: on a
+// bonus-aware instantiation of it; for generation 6 the ring need of the DP and the total of its own LDS plan (its footprint class).
+struct KernelChoice { int generation; char ib; int v6_total; V6Ring v6_ring; };
+static inline KernelChoice choose_kernel(const DpFacts &d, const BatchShape &s, const PrepOptions &o, bool force_v1)
+{
+    KernelChoice k = {0, 0, 0, {{32, 32, V6_RHCOLS}, 4, {1, 1, 1}}};
+    int gen = 0;
+    const bool v1 = force_v1 || o.force_v1;
+    if (d.kind == 0 && !d.rect && !v1 && !o.no_v7) gen = 7;      // DPunit: strips without gap state (the rectangular engine: g2g_forward_kernel)
+    if (d.kind == 3 && !v1 && !o.no_v8) {
+        // DPunit_nv: strips with the members' gap lengths in registers, for the member counts selAlnMode sends this way
+        const int an = d.a.many, bn = d.b.many, ck = d.crg2_kind;
+        const bool fits = ck == 11 ? (an == 1 && bn == 1) : (ck == 120 || ck == 121) ? (an == 1 && bn <= 5) :
+                          (ck == 210 || ck == 211) ? (an <= 5 && bn == 1) : (ck == 220 || ck == 221) ? (an <= 3 && bn <= 3) : false;
+        if (fits && d.a.gapdens && d.b.gapdens && d.a.postgapdens && d.b.postgapdens && (!(ck & 1) || ck == 11 || (d.a.weight && d.b.weight))) gen = 8;
+    }
+    if ((d.kind == 1 || d.kind == 2) && !v1 && d.a.len + d.b.len < 65000) {
+        // _pf: one lane per cell with rank-form merges (v6) when the rows' static lists fit the register file
+        bool v6 = s.v6_on && !o.force_v2 && !o.no_v6 && d.kind == 2 && d.a.maxlist <= (d.noll == 3 ? G2G_V6_NA3 : G2G_V6_NA) && d.a.r_from_t && d.b.r_from_t;
+        if (v6) {
+            k.v6_ring = v6_ring_need(d.b.off, d.b.left, d.b.right);
+            k.v6_total = v6_layout(v6_rows_bytes(d.capa, d.capb, d.noll), (d.capa + 3) & ~3, k.v6_ring).total;
+            v6 = k.v6_total <= std::max(o.v6_small, o.v6_large);
+        }
+        if (v6) gen = 6;
+        else if (!o.force_v2 && !o.no_areg && d.kind == 1 && d.a.maxlist <= G2G_V3_NA && d.a.r_from_t && v3_need(d, s.v3_cols, true).total <= (int) V2_LDS_MAX) gen = 3;
+        else {
+            // lists too long for registers: the LDS-list one-lane-per-cell kernel, unless its LDS footprint leaves fewer than
+            // three waves per CU and the 8-lanes-per-cell kernel fits (a 512 x 2048 nt DNA sweep with 17-32 entry lists and
+            // Noll 3: 87 KB per strip; 28.3 s with it, 22.4 s on v2)
+            const bool v2fit = v2_fits(d, s.v2_threads);
+            const int v3tot = (!o.force_v2 && d.kind == 1) ? v3_need(d, s.v3_cols).total : (int) V2_LDS_MAX + 1;
+            if (v3tot <= (int) V2_LDS_MAX && (v3tot <= (int) V2_LDS_MAX / 3 || !v2fit || o.no_areg)) gen = 2;
+            else if (v2fit) gen = 1;
+        }
+    }
+    if (d.nbonus) {
+        // The intron-position bonus: g2g_forward_kernel (v1), and the bonus-aware instantiations of the strips without gap
+        // state (v7), of the naive-record strips (v8) and of the 8-lanes-per-cell strips (v2, sweep mode) -- not v3 / v3r / v6
+        // (register-bound), so an annotated _hf / _pf DP goes to v2 whatever would otherwise have claimed it, within v2's own
+        // limits.  NO_STRIP_BONUS: v1 for all of them, as before the strips knew the bonus.
+        const int was = gen;
+        gen = 0;
+        if (!o.no_strip_bonus) {
+            if (was == 7 || was == 8) gen = was;
+            else if (was >= 1 && was <= 6 && (d.kind == 1 || d.kind == 2) && s.v2_sweep && v2_fits(d, s.v2_threads)) gen = 1;
+        }
+        k.ib = gen ? 1 : 0;
+    }
+    k.generation = gen;
+    return k;
+}
+
+#ifdef G2G_DEVICE_H_                // (diag_rows lives in g2g_device.h beside the descriptors, which are HIP types: the engine's units see it)
+// in-band cells of a DP and its widest anti-diagonal (the stride of its trace)
+struct BandCells { long long cells; int tstride; };
+static inline BandCells band_cells(int al, int ar, int bl, int br, int lw, int up)
+{
+    BandCells r = {0, 1};
+    for (int dd = al + bl; dd <= (ar - 1) + (br - 1); ++dd) {
+        int mlo, mhi;
+        diag_rows(dd, al, ar, bl, br, lw, up, &mlo, &mhi);
+        const int c = mhi - mlo + 1;
+        if (c > 0) r.cells += c;
+        if (c > r.tstride) r.tstride = c;
+    }
+    return r;
+}
+#endif
+
+// ---- (g) prepare: the queues of a batch ------------------------------------------------------------------------------------
+// Tiles: (strip i of R rows) x (block j of C columns, C chosen per batch); per variant slot one queue ordered by wavefront i + j,
+// headed by the boundary chains of its sweep-mode DPs; one completion flag per tile slot (empty slots count as done for ever).
+// Everything g2g_batch_prepare uploads for the persistent kernels, and the LDS plans of the launches, as values.
+struct QueuePlan {
+    int bad;                        // index of a DP whose kernel has no variant slot (-1: none; nothing else is valid otherwise)
+    std::vector<V2Tile> tiles;      // in upload order; slot v owns [var_off[v], var_off[v + 1])
+    int var_off[G2G_NVAR + 1];
+    long long var_cells[G2G_NVAR];  // in-band cells of the DPs of slot v
+    std::vector<int> flags;         // the initial image of d_flags: queue heads, wait header, tile flags / progress words, then
+    int fail_off, dump_off, xq_off; // ... the per-DP fail flags, the first time-out's dump area, the queue heads of the slots from G2G_PLAN_HDR on
+    std::vector<int> ip;            // DPs whose boundary chains run in the prologue kernel (the others': as queue entries)
+    size_t lds2p, simtile_lds;      // LDS of the prologue launch and of the tiled column-score kernel
+    int v2_maxrows, v2_maxcols;     // longest a-range / b-range among the DPs on strips
+    V3Lds v3lds[8];
+    V6Lds v6lds[6];
+    std::string v6_ring_plan;       // option V6_RING_PLAN: per v6 launch that has strips "<class x 2 + Noll 3>:<S of the s ring>,<S of the t ring>,<T>,<LDS bytes>", joined by ';'
+};
+static inline QueuePlan queue_plan(const DpFacts *facts, const KernelChoice *choice, const long long *cells, const BatchShape &s, const PrepOptions &o, int n)
+{
+    QueuePlan Q;
+    Q.bad = -1; Q.lds2p = 0; Q.simtile_lds = 0; Q.v2_maxrows = 1; Q.v2_maxcols = 1; Q.fail_off = Q.dump_off = Q.xq_off = 0;
+    for (int v = 0; v < G2G_NVAR; ++v) Q.var_cells[v] = 0;
+    for (int v = 0; v <= G2G_NVAR; ++v) Q.var_off[v] = 0;
+    std::vector<std::vector<std::vector<V2Tile> > > q(G2G_NVAR);  // [variant][wavefront] -> tiles
+    std::vector<int> &flags = Q.flags;
+    flags.assign(G2G_PLAN_HDR + G2G_HDRN, 0);         // queue heads, then the header of the waits (g2g_wait_ge)
+    std::vector<V2Tile> pre[G2G_NVAR];                // boundary chains of sweep-mode DPs: they head their variant's queue
+    int v6rows[6] = {0, 0, 0, 0, 0, 0}, v6ca4[6] = {0, 0, 0, 0, 0, 0};
+    V6Ring v6rs[6];
+    for (int v = 0; v < 6; ++v) { const V6Ring r0 = {{32, 32, V6_RHCOLS}, 4, {1, 1, 1}}; v6rs[v] = r0; }
+    V3Need need[8];
+    for (int v = 0; v < 8; ++v) { const V3Need z = {0, 0, 0, 0, 0}; need[v] = z; }
+    for (int i = 0; i < n; ++i) {
+        const DpFacts &d = facts[i];
+        const int gen = choice[i].generation;
+        if (d.kind < 0 || !gen) continue;
+        Q.lds2p = std::max(Q.lds2p, 5 * strip_record_bytes(gen, d.kind, d.capa, d.capb) + 64);
+        Q.v2_maxrows = std::max(Q.v2_maxrows, d.a.right - d.a.left);
+        Q.v2_maxcols = std::max(Q.v2_maxcols, d.b.right - d.b.left);
+        if (d.a.nelm > 0 && sim_tiled_kind(d.sim2_kind)) {        // a's profile rows + b's frequency vectors or residues
+            const bool vecb = d.sim2_kind == 33 || d.sim2_kind == 330;
+            Q.simtile_lds = std::max(Q.simtile_lds, (size_t) 8 * SIM_TR * ((d.a.nelm - d.a.felm + 1) & ~1) + (vecb ? (size_t) 8 * SIM_TC * (d.b.felm > 0 ? d.b.felm : 0) : (size_t) SIM_TC * d.b.many) + 64);
+        }
+        const int al = d.a.left, ar = d.a.right, bl_ = d.b.left, br = d.b.right;
+        const int R = gen >= 2 ? 64 : s.v2_threads / 8;
+        const bool swp3 = (gen == 3 || gen == 2) && d.kind == 1 && s.v3_sweep;   // one tile per strip, pipelined (kind 1 only: no column pool)
+        const bool swp2 = (gen == 1 && s.v2_sweep) || gen >= 6;      // (v6 and v7 know sweep mode only)
+        const int C = (swp3 || swp2) ? (1 << 20) : gen >= 2 ? s.v3_cols : s.v2_cols;
+        const int nstrip = (ar - al + R - 1) / R, nblk = (br - bl_ + C - 1) / C;
+        // (one LDS plan per launch = the largest of its DPs: DPs whose column lists need a big ring get a launch of their own,
+        //  or a handful of balanced divisions would cost every strip of the sweep its occupancy)
+        const int v6fp = gen != 6 ? 0 : choice[i].v6_total > o.v6_small ? 2 : choice[i].v6_total > V6_CLASS_A ? 1 : 0;      // footprint class A / B / C
+        const int var = variant_slot(gen, d.kind, d.noll, choice[i].ib != 0, v6fp);
+        if (var < 0) { Q.bad = i; return Q; }
+        Q.var_cells[var] += cells[i];
+        if (gen == 6) {
+            const int v6cls = variant_v6_index(var);
+            v6rows[v6cls] = std::max(v6rows[v6cls], v6_rows_bytes(d.capa, d.capb, d.noll));
+            v6ca4[v6cls] = std::max(v6ca4[v6cls], (d.capa + 3) & ~3);
+            v6_ring_max(v6rs[v6cls], choice[i].v6_ring);
+        } else if (gen >= 2 && gen < 7) {
+            const V3Need nd = v3_need(d, C, gen == 3);
+            V3Need &x = need[variant_v3_index(var)];
+            x.rows_bytes = std::max(x.rows_bytes, nd.rows_bytes); x.ca4 = std::max(x.ca4, nd.ca4);
+            x.apool = std::max(x.apool, nd.apool); x.bpool = std::max(x.bpool, nd.bpool);
+        }
+        const bool cq = (!o.no_chainq && (swp2 || swp3)) || gen >= 7;      // (v7's and v8's chains always run as queue entries: the prologue kernel knows the gap-profile kinds only)
+        int ftop = -1, fleft = -1;
+        if (cq) {
+            ftop = (int) flags.size(); fleft = ftop + G2G_FSTRIDE;
+            flags.resize(flags.size() + 2 * G2G_FSTRIDE, 0);
+            V2Tile T;
+            T.prob = i; T.tj = 0; T.nsteps = 0; T.dep_up = T.dep_left = T.dep_diag = T.dep_war = -1;
+            T.ti = -1; T.self = ftop; pre[var].push_back(T);
+            T.ti = -2; T.self = fleft; pre[var].push_back(T);
+        } else Q.ip.push_back(i);
+        const int fbase = (int) flags.size();
+        flags.resize(flags.size() + (size_t) nstrip * nblk * G2G_FSTRIDE, 0x7fffffff);
+        for (int ti = 0; ti < nstrip; ++ti) {
+            const int m0 = al + ti * R;
+            for (int tj = 0; tj < nblk; ++tj) {
+                const int c0 = bl_ + tj * C, c1 = std::min(c0 + C, br);
+                const int cbase = std::max(std::max(m0 + d.lw, bl_), c0);
+                int nsteps = 0;
+                for (int t = 0; t < R && m0 + t < ar; ++t) {
+                    const int m = m0 + t;
+                    const int lo = std::max(std::max(m + d.lw, bl_), c0), hi = std::min(std::min(m + d.up + 1, br), c1);
+                    if (hi > lo) nsteps = std::max(nsteps, hi - cbase + t);
+                }
+                if (!nsteps) continue;
+                V2Tile T;
+                T.prob = i; T.ti = ti; T.tj = tj; T.nsteps = nsteps;
+                T.self = fbase + (ti * nblk + tj) * G2G_FSTRIDE;
+                T.dep_up = ti > 0 ? T.self - nblk * G2G_FSTRIDE : ftop;             // sweep mode: the top chain is strip 0's "strip above"
+                T.dep_left = tj > 0 ? T.self - G2G_FSTRIDE : fleft;
+                T.dep_diag = (ti > 0 && tj > 0) ? T.self - (nblk + 1) * G2G_FSTRIDE : -1;
+                T.dep_war = (ti > 1 && tj + 1 < nblk) ? T.self - (2 * nblk - 1) * G2G_FSTRIDE : -1;
+                flags[T.self] = 0;
+                const int k = ti + tj;
+                if ((int) q[var].size() <= k) q[var].resize(k + 1);
+                q[var][k].push_back(T);
+            }
+        }
+    }
+    std::vector<V2Tile> &all = Q.tiles;
+    for (int v = 0; v < G2G_NVAR; ++v) {
+        Q.var_off[v] = (int) all.size();
+        all.insert(all.end(), pre[v].begin(), pre[v].end());
+        for (size_t k = 0; k < q[v].size(); ++k) all.insert(all.end(), q[v][k].begin(), q[v][k].end());
+    }
+    Q.var_off[G2G_NVAR] = (int) all.size();
+    for (int v = 0; v < 6; ++v) Q.v6lds[v] = v6_layout(v6rows[v], v6ca4[v], v6rs[v]);
+    for (int sl = 0; sl < G2G_NVAR; ++sl) {
+        const int v = variant_v6_index(sl);
+        if (v < 0 || Q.var_off[sl + 1] == Q.var_off[sl]) continue;
+        char buf[96];
+        snprintf(buf, sizeof buf, "%s%d:%d,%d,%d,%d", Q.v6_ring_plan.empty() ? "" : ";", v, Q.v6lds[v].rs[0], Q.v6lds[v].rs[1], Q.v6lds[v].rtail, Q.v6lds[v].total);
+        Q.v6_ring_plan += buf;
+    }
+    for (int v = 0; v < 8; ++v) Q.v3lds[v] = v3_layout(need[v].rows_bytes, need[v].ca4, need[v].apool, need[v].bpool, s.v3_cols);
+    // test hook: INJECT_STALL=<i> makes the first strip / tile of problem i depend on a flag nobody ever writes
+    if (o.inject) {
+        const int never = (int) flags.size();
+        flags.resize(flags.size() + G2G_FSTRIDE, 0);
+        for (size_t k = 0; k < all.size(); ++k)
+            if (all[k].prob == o.inject_victim && all[k].ti >= 0) { all[k].dep_up = never; break; }
+    }
+    Q.fail_off = (int) flags.size();                  // per-DP fail flags behind the tile flags
+    flags.resize(flags.size() + (size_t) (n > 0 ? n : 1), 0);
+    Q.dump_off = (int) flags.size();                  // the first time-out's view of its whole DP (g2g_wait_ge: G2G_DUMP_STRIPS strips x G2G_DUMP_WORDS words)
+    flags.resize(flags.size() + 2 + G2G_DUMP_WORDS * G2G_DUMP_STRIPS, 0);
+    Q.xq_off = (int) flags.size();                    // queue heads of the bonus-aware variants
+    flags.resize(flags.size() + (G2G_NVAR - G2G_PLAN_HDR), 0);
+    return Q;
+}
 #endif

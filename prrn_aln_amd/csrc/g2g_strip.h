@@ -49,7 +49,7 @@ template <class T> __device__ __forceinline__ GLB T *glbw(T *p) { return (GLB T 
 // execute at the memory side and leave no copy of the line in anybody's L2.  MEASURED (three whole refinements each way, round
 // 4): the events went on with both remedies in place (1, 1 and 3 per run), and the RMW polls cost 4 % -- the hypothesis is refuted,
 // the split lines stay (they cost nothing), the polls and publishes are plain agent-scope loads and stores again.
-#define G2G_FSTRIDE 64               // ints between two tile flags / progress words
+#include "g2g_lds.h"                 // G2G_FSTRIDE (ints between two tile flags / progress words), G2G_HDRN, G2G_DUMP_STRIPS / _WORDS: the host plans with them
 #define G2G_DIAG 32                  // offset of a strip's diagnostics line from its progress word
 #ifdef G2G_POLL_RMW
 #define G2G_POLL(p) __hip_atomic_fetch_or((int *) (p), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -58,10 +58,7 @@ template <class T> __device__ __forceinline__ GLB T *glbw(T *p) { return (GLB T 
 #define G2G_POLL(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define G2G_POST(p, v) __hip_atomic_store((int *) (p), (int) (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #endif
-#define G2G_DUMP_STRIPS 580           // strips of one DP the first time-out dumps for the host ...
-#define G2G_DUMP_WORDS 11             // ... words each: progress word, HW_ID, three markers, two publish columns, (step, place) of two waves
 #define G2G_GAP_TICKS 400000ull       // 4 ms of s_memrealtime: more than ten times what 64 polls take
-#define G2G_HDRN 104                  // header words: 4 + the snapshot (want, seen, offset of the polled word, the words at and below it; [48, 64): per-wave heartbeats); G2G_HDR + G2G_HDRN is a multiple of G2G_FSTRIDE, so every progress line IS one 128-byte line
 __device__ __forceinline__ int g2g_wait_ge(const int *p, const int want, int *hdr, int *failp, const int slot)
 {
     int v = G2G_POLL(p);

@@ -1,10 +1,13 @@
-"""The host-side planning of a batch run (prrn_aln_amd/csrc/g2g_plan.h: the variant table, the CU shares, the launch list, the
-text of a time-out report) without a GPU: tests/host/plan_main.cc runs a fixed list of cases, built with g++ under ASan + UBSan,
+"""The host-side planning of a batch (prrn_aln_amd/csrc/g2g_plan.h) without a GPU -- of a run: the variant table, the CU shares,
+the launch list, the text of a time-out report; of prepare: the kernel of a DP (choose), the shape of a batch (shape), its tile
+queues, flag image and LDS plans (queues).  tests/host/plan_main.cc runs a fixed list of cases, built with g++ under ASan + UBSan,
 and its output is compared with tests/golden/host_plan/*.txt.
 
 The expectation files were written by the same program compiled against the blocks of g2g_batch_run / batch_prepare_impl as they
 stood before they moved into g2g_plan.h (the slot arithmetic, the apportionment block, the four launch loops with the launches
-recorded instead of made, the report formatter), so they pin that behaviour, not the header's."""
+recorded instead of made, the report formatter; for the three prepare sections choose_kernel, v2_lds_bytes, v3_layout, v3_need,
+the tile-width block and build_queues with g2g_opt a lookup in the case's options and the HIP copies recorded), so they pin that
+behaviour, not the header's."""
 import os
 import subprocess
 
@@ -22,7 +25,7 @@ def plan_main(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("what", ["slots", "shares", "launches", "report"])
+@pytest.mark.parametrize("what", ["slots", "shares", "launches", "report", "choose", "shape", "queues"])
 def test_plan_matches_recorded_behaviour(plan_main, what):
     p = subprocess.run([plan_main, what], capture_output=True, text=True)
     assert p.returncode == 0 and p.stderr == "", p.stderr            # (a sanitizer report goes to stderr)
