@@ -450,6 +450,45 @@ int        g2g_alnscored_batch(g2g_ctx *ctx, const g2g_params *prm, int nseq, co
 int        g2g_alignb_ng_batch(g2g_ctx *ctx, const g2g_params *prm, int nseq, const g2g_dseq *seqs, int npairs,
                                const int32_t *ia, const int32_t *ib, double *scr, g2g_skl **skl, int *nskl, int32_t *status);
 
+/* ---- k-mer composition distances between unaligned single sequences ---------------------------------------------------
+ * <-> FTYPE* calcdist_kmer(Seq** seqs, int nn, int inm, Strlist*& snm) (reference src/qdiv.cc:245-282), the distance matrix
+ * DistMat(Seq**, nn) holds (src/phyl.cc:515-528) when makemsa runs with algmode.any == Composition (src/prrn5.cc:976-979), and
+ * AdjacentMat::dist_kmer per candidate pair (src/adjmat.cc:90-97): the cheap guide-tree distance, no DP.
+ *   words : Kcomp::makeHash (qdiv.cc:61-80) with the continuous seed (Bitpat_wq::word / flaw, src/bitpat.cc:168-185).  The scan reads
+ *           the residues left .. right - k - 1 and counts a word wherever the last k residues read were all elementary (the 20
+ *           amino acids, or A C G T): an ungapped sequence of elementary residues has max(0, (right - left) - 2 k + 1) words.
+ *           Any other residue (X, B, Z, N and the other ambiguity codes, gap, nil) breaks the word -- the reference reads table
+ *           entries it never wrote for them (bitpat.cc:76-86); here no word that contains one is counted.
+ *   pair  : qdiv (qdiv.cc:179-232, many == 1): s = the sum over shared words of the smaller count, f = s / min(Ta, Tb) with
+ *           Ta, Tb the word totals, d = 1 - f; then by DistMes (src/aln.h:54)
+ *             0 QFdiv d   1 QFidn f   6 NJuCa jukcan(d)
+ *           and, after f = 0.18704 * log((0.00501 + f) / (0.00501 + 1.)) + 1., d = 1. - f,
+ *             2 QCdiv d   3 QCidn f   4 QJuCa jukcanpro(d)   5 Qpamd pamcorrect(d) / 100. (corr_mhits == 0)
+ *           (jukcan / jukcanpro / pamcorrect: src/divseq.cc:107-139; out of range gives OUTOFRANGE = 1024).  The stored distance
+ *           is 100 * qdiv (kcmp_main, qdiv.cc:239).  A member without any word gives 0 / 0 = NaN with every partner, as in the
+ *           reference.  Defaults (qdiv.cc:32-33): protein k = 5 with Qpamd, DNA k = 10 with QJuCa (DNA does go through jukcanpro).
+ * The parameters are taken literally: resetqdiv's swapping of one molecule's defaults for the other's (qdiv.cc:45-57) is not
+ * reproduced.  The device (csrc/g2g_kmer.hip) sorts and counts the words and intersects the lists -- integers only: s, Ta, Tb per
+ * pair; the doubles are formed on the host in the reference's operation order.  Nothing is sorted on the host.
+ * Limits (else G2G_ERR_ARG): k 1 .. 6 for protein, 1 .. 15 for DNA (beyond them the reference's 32-bit (queue * nalpha + c) % TabSize,
+ * bitpat.cc:183, no longer forms the true words); measure -1 .. 6; reserved 0; 2 <= nseq, and nseq <= 4096 in the all-pairs form;
+ * at most 16384 word positions ((right - left) - 2 k + 1) per sequence -- g2g_last_error names the sequence; 0 <= left <= right <= len.
+ * Not on this path: reduced alphabets, spaced seeds, profiles of groups (many > 1), corr_mhits != 0.
+ * (Entry points added without a change of g2g_abi_version.) */
+typedef struct g2g_kmer_params {
+    int32_t molc;      /* 1 PROTEIN, 2 DNA */
+    int32_t k;         /* 0: the reference's default (5 / 10) */
+    int32_t measure;   /* DistMes value 0..6; -1: the default (Qpamd / QJuCa) */
+    int32_t reserved;
+} g2g_kmer_params;
+/* dist[p] = 100 * qdiv(a, b); counts (may be NULL): s, Ta, Tb per pair.
+   ia == ib == NULL: all pairs, pair (i < j) at j (j - 1) / 2 + i, npairs = nseq (nseq - 1) / 2.
+   A pair (i, i) is legal.  Arguments are checked before the device is asked for. */
+int        g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int nseq, const g2g_dseq *seqs,
+                               int npairs, const int32_t *ia, const int32_t *ib, double *dist, int32_t *counts);
+/* host only, no context: the closed form from the three integers of each pair */
+int        g2g_kmer_dist_from_counts(const g2g_kmer_params *kp, int npairs, const int32_t *counts, double *dist);
+
 #ifdef __cplusplus
 }
 #endif

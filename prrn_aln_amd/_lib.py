@@ -85,6 +85,9 @@ def lib():
     L.g2g_ktree_from_msa.argtypes = [C.c_void_p, C.c_int, C.c_int, _abi.c_u8p, C.POINTER(_abi.KTreeOut)]
     L.g2g_ktree_free.restype = None
     L.g2g_ktree_free.argtypes = [C.POINTER(_abi.KTreeOut)]
+    L.g2g_kmer_dist_batch.argtypes = [C.c_void_p, C.POINTER(_abi.KmerParams), C.c_int, C.POINTER(_abi.DSeq), C.c_int,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), _abi.c_f64p, C.POINTER(C.c_int32)]
+    L.g2g_kmer_dist_from_counts.argtypes = [C.POINTER(_abi.KmerParams), C.c_int, C.POINTER(C.c_int32), _abi.c_f64p]
     bind_level1(L)
     _lib = L
     return L

@@ -6,7 +6,9 @@ sequences of a family, as the reference's dpscore() computes them (src/phyl.cc:2
     dist[i,j] = 100 * (1 - (score + u * |len_i - len_j| / 2) / sqrt(scr1[i] * scr1[j]))   (alnscore2dist, src/aln2.cc:325-333)
 
 All DPs of the N (N - 1) / 2 pairs go to the device as ONE batch (g2g_alnscored_batch: the sequences are uploaded once, a
-pair is two indices).  There is no CPU fallback: without libg2g.so / a GPU the calls raise."""
+pair is two indices).  For families too large for one DP per pair, kmer_distance gives the reference's k-mer composition
+distance (calcdist_kmer, src/qdiv.cc:245-282) in the same layout.  There is no CPU fallback: without libg2g.so / a GPU the
+calls raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -78,6 +80,60 @@ def msa_divergence(ctx, codes: np.ndarray):
     if rc != 0:
         raise G2GError("g2g_msa_divergence rc=%d: %s" % (rc, last_error()))
     return dist, counts
+
+
+def _kmer_params(molc: int, k: int, measure: int) -> "_abi.KmerParams":
+    kp = _abi.KmerParams()
+    kp.molc, kp.k, kp.measure, kp.reserved = int(molc), int(k), int(measure), 0
+    return kp
+
+
+def kmer_dist_from_counts(counts: np.ndarray, molc: int, k: int = 0, measure: int = -1) -> np.ndarray:
+    """g2g_kmer_dist_from_counts (host only): 100 x qdiv from the three integers (s, Ta, Tb) of each pair, the reference's
+    closed forms in its operation order (src/qdiv.cc:202-231, 239)"""
+    cnt = np.ascontiguousarray(counts, np.int32).reshape(-1, 3)
+    dist = np.zeros(len(cnt), np.float64)
+    kp = _kmer_params(molc, k, measure)
+    rc = lib().g2g_kmer_dist_from_counts(C.byref(kp), len(cnt), cnt.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(_abi.c_f64p))
+    if rc != 0:
+        raise G2GError("g2g_kmer_dist_from_counts rc=%d: %s" % (rc, last_error()))
+    return dist
+
+
+def kmer_distance(ctx, seqs: Sequence, molc: int, k: int = 0, measure: int = -1, ia=None, ib=None, want_counts: bool = False):
+    """g2g_kmer_dist_batch: the k-mer composition distance of the reference's calcdist_kmer (src/qdiv.cc:245-282), 100 x qdiv,
+    between unaligned single sequences -- all pairs (pair (i < j) is entry j (j - 1) / 2 + i, the layout KTree.from_dist takes:
+    the guide tree is KTree.from_dist(dist, with_weights=False)) or the index pairs (ia, ib).  k = 0 / measure = -1: the
+    reference's defaults (protein k 5 with Qpamd, DNA k 10 with QJuCa).  A sequence is an array of residue codes, or a tuple
+    (codes, left, right) for a range inside a longer buffer.  With want_counts: (dist, counts int32[npairs, 3] = s, Ta, Tb)."""
+    if (ia is None) != (ib is None):
+        raise ValueError("ia and ib come together")
+    ds = (_abi.DSeq * max(len(seqs), 1))()
+    keep = []
+    for n, s in enumerate(seqs):
+        s, left, right = s if isinstance(s, tuple) else (s, 0, None)
+        x = np.ascontiguousarray(s, np.uint8)
+        keep.append(x)
+        ds[n].res = x.ctypes.data_as(_abi.c_u8p)
+        ds[n].len, ds[n].left, ds[n].right = len(x), left, len(x) if right is None else right
+    nseq = len(seqs)
+    if ia is None:
+        npairs = max(nseq * (nseq - 1) // 2, 0)
+        pa = pb = None
+    else:
+        ia = np.ascontiguousarray(ia, np.int32); ib = np.ascontiguousarray(ib, np.int32)
+        if ia.shape != ib.shape or ia.ndim != 1:
+            raise ValueError("ia and ib are two index vectors of one length")
+        npairs = len(ia)
+        pa, pb = ia.ctypes.data_as(C.POINTER(C.c_int32)), ib.ctypes.data_as(C.POINTER(C.c_int32))
+    dist = np.zeros(npairs, np.float64)
+    counts = np.zeros((npairs, 3), np.int32)
+    kp = _kmer_params(molc, k, measure)
+    rc = lib().g2g_kmer_dist_batch(ctx._h, C.byref(kp), nseq, ds, npairs, pa, pb, dist.ctypes.data_as(_abi.c_f64p),
+                                   counts.ctypes.data_as(C.POINTER(C.c_int32)) if want_counts else None)
+    if rc != 0:
+        raise G2GError("g2g_kmer_dist_batch rc=%d: %s" % (rc, last_error()))
+    return (dist, counts) if want_counts else dist
 
 
 def alignb_ng_batch(ctx, prm: "_abi.Params", seqs: Sequence[np.ndarray], ia: Sequence[int], ib: Sequence[int]):
