@@ -198,6 +198,255 @@ __device__ double sim2(const DevProb &P, int m, int n)
     return 0;
 }
 
+// ---- block scorer: sim2 of rows x 64 columns, for the strips' column-score blocks (simblk_fill_block, g2g_strip.h) ------------------
+// The same sums as sim2(), element by element in ascending order, product and sum rounded separately -- scheduled for a wave
+// that has nobody to hide a memory wait behind: the scorer is chosen once per block, what depends on the column alone (b's
+// residues, b's vector entries) is read once per block and kept in registers, what is wave-uniform (weights, a row's vector or
+// residues) is read by ONE load with a lane per element and handed out with v_readlane, and a row issues all its loads before
+// it waits.  Lane <-> column; all 64 lanes stay active (a lane beyond b.right reads column b.right - 1 and stores nothing).
+// Lists longer than the registers hold go in chunks (SB_CR residues / SB_VC vector entries / 64 lane-held elements); the sum
+// of a cell is then carried through its place in the block, which is exact because the sum is sequential.
+#define SIMG __attribute__((address_space(1)))
+typedef const SIMG double *sb_dp;
+typedef const SIMG uint8_t *sb_bp;
+#define SB_G 8                            /* gathers in flight per wait */
+#define SB_CR 32                          /* residues of a column held in registers (four to a dword) */
+#ifndef G2G_SIMBLK_VC
+#define G2G_SIMBLK_VC 24                  /* vector entries of a column held in registers */
+#endif
+struct SimRows {                          // the block: lane's column n (nn: clamped into b), rows m0 + r, r = r0, r0 + rstep, ... < rows
+    SIMG double *dst; int n, nn, m0, r0, rstep, rows, lane;
+};
+__device__ __forceinline__ double sb_rl(double x, int l)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
+}
+// a lane-held value stays in its VGPR: without this the v_readlane copies of a block's weights are hoisted out of the row loop
+// into SGPRs the strip kernels do not have
+#define SB_KEEP(x) asm volatile("" : "+v"(x))
+// the SB_G loads of a batch have all been issued and have all arrived: ONE wait here, and no load sinks into the (wave-uniform)
+// branches around the sums behind it
+__device__ __forceinline__ void sb_arrived(double (&x)[SB_G])
+{
+    static_assert(SB_G == 8, "sb_arrived names every element");
+    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
+}
+__device__ __forceinline__ int sb_min(int x, int y) { return x < y ? x : y; }
+__device__ __forceinline__ void sb_store(const DevProb &P, const SimRows &R, int r, double s)
+{
+    const int m = R.m0 + r;
+    int nlo = m + P.lw; if (nlo < P.b.left) nlo = P.b.left;
+    int nhi = m + P.up + 1; if (nhi > P.b.right) nhi = P.b.right;
+    if (R.n >= nlo && R.n < nhi) R.dst[r * 64] = s;
+}
+// lane l <- first residue of row m0 + l (kinds that pick a matrix row / a vector entry by a's only member)
+__device__ __forceinline__ int sb_rows_res0(const DevProb &P, const SimRows &R)
+{
+    const int m = sb_min(R.m0 + R.lane, P.a.right - 1);
+    return ((sb_bp) P.a.seq)[(size_t) (m + 1) * P.a.many];
+}
+// up to SB_CR residues of the lane's column from member j0 on, four to a dword; lane l <- b.weight[j0 + l]
+__device__ __forceinline__ void sb_col_res(const DevSide &b, const SimRows &R, int j0, int cnt, unsigned (&cr)[SB_CR / 4])
+{
+    const sb_bp br = (sb_bp) b.seq + (size_t) (R.nn + 1) * b.many + j0;
+#pragma unroll
+    for (int q = 0; q < SB_CR / SB_G; ++q) {
+        unsigned x[SB_G];
+        if (q * SB_G < cnt) {
+#pragma unroll
+            for (int t = 0; t < SB_G; ++t) x[t] = br[sb_min(q * SB_G + t, cnt - 1)];
+        } else {
+#pragma unroll
+            for (int t = 0; t < SB_G; ++t) x[t] = 0;
+        }
+#pragma unroll
+        for (int t = 0; t < SB_G; t += 4) cr[(q * SB_G + t) >> 2] = x[t] | (x[t + 1] << 8) | (x[t + 2] << 16) | (x[t + 3] << 24);
+    }
+}
+__device__ __forceinline__ double sb_lane_w(const double *w, const SimRows &R, int j0, int cnt)
+{
+    return ((sb_dp) w)[j0 + sb_min(R.lane, cnt - 1)];
+}
+// s += base[res_j] (* w_j), j = 0 .. cnt-1 of a chunk: SB_G gathers, one wait, SB_G sums
+template <bool W>
+__device__ __forceinline__ double sb_gather(const sb_dp base, const unsigned (&cr)[SB_CR / 4], const double wl, const int cnt, double s)
+{
+#pragma unroll
+    for (int q = 0; q < SB_CR / SB_G; ++q) {
+        if (q * SB_G < cnt) {
+            double x[SB_G];
+#pragma unroll
+            for (int t = 0; t < SB_G; ++t) { const int j = q * SB_G + t; x[t] = base[(cr[j >> 2] >> (8 * (j & 3))) & 255u]; }
+            sb_arrived(x);
+#pragma unroll
+            for (int t = 0; t < SB_G; ++t) {
+                const int j = q * SB_G + t;
+                if (j < cnt) { if (W) s += x[t] * sb_rl(wl, j); else s += x[t]; }
+            }
+        }
+    }
+    return s;
+}
+// 120 / 121 (MTX: the row of the matrix a's residue picks) and 320 / 321 (a's profile vector), gathered by b's residues
+template <bool MTX, bool W>
+__device__ __forceinline__ void sb_by_colres(const DevProb &P, const SimRows &R)
+{
+    const DevSide &a = P.a, &b = P.b;
+    const int ar0 = MTX ? sb_rows_res0(P, R) : 0;
+    for (int j0 = 0; j0 < b.many; j0 += SB_CR) {
+        const int cnt = sb_min(SB_CR, b.many - j0);
+        unsigned cr[SB_CR / 4];
+        sb_col_res(b, R, j0, cnt, cr);
+        double wl = W ? sb_lane_w(b.weight, R, j0, cnt) : 0;
+        for (int r = R.r0; r < R.rows; r += R.rstep) {
+            const int m = R.m0 + r;
+            if (m >= a.right) break;
+            const sb_dp base = MTX ? (sb_dp) P.simmtx + (size_t) __builtin_amdgcn_readlane(ar0, r) * P.simdim
+                                   : (sb_dp) a.pseq + (size_t) (m + 1) * a.nelm + a.felm;
+            double s = 0;
+            if (j0) s = R.dst[r * 64];
+            SB_KEEP(wl);
+            s = sb_gather<W>(base, cr, wl, cnt, s);
+            sb_store(P, R, r, s);
+        }
+    }
+}
+// 210 / 211 (MTX: the row of the matrix b's residue picks) and 230 / 231 (b's profile vector), gathered by a's residues: the
+// lane's base stays, a row's residues come one row ahead with a lane per member
+template <bool MTX, bool W>
+__device__ __forceinline__ void sb_by_rowres(const DevProb &P, const SimRows &R)
+{
+    const DevSide &a = P.a, &b = P.b;
+    const sb_dp base = MTX ? (sb_dp) P.simmtx + (size_t) ((sb_bp) b.seq)[(size_t) (R.nn + 1) * b.many] * P.simdim
+                           : (sb_dp) b.pseq + (size_t) (R.nn + 1) * b.nelm + b.felm;
+    for (int i0 = 0; i0 < a.many; i0 += 64) {
+        const int cnt = sb_min(64, a.many - i0);
+        const int li = i0 + sb_min(R.lane, cnt - 1);
+        double wl = W ? sb_lane_w(a.weight, R, i0, cnt) : 0;
+        int ar_nx = ((sb_bp) a.seq)[(size_t) (sb_min(R.m0 + R.r0, a.right - 1) + 1) * a.many + li];
+        for (int r = R.r0; r < R.rows; r += R.rstep) {
+            const int m = R.m0 + r;
+            if (m >= a.right) break;
+            const int ar = ar_nx;
+            SB_KEEP(wl);
+            ar_nx = ((sb_bp) a.seq)[(size_t) (sb_min(m + R.rstep, a.right - 1) + 1) * a.many + li];
+            double s = 0;
+            if (i0) s = R.dst[r * 64];
+            for (int q = 0; q < cnt; q += SB_G) {
+                double x[SB_G];
+#pragma unroll
+                for (int t = 0; t < SB_G; ++t) x[t] = base[__builtin_amdgcn_readlane(ar, sb_min(q + t, cnt - 1))];
+                sb_arrived(x);
+#pragma unroll
+                for (int t = 0; t < SB_G; ++t)
+                    if (q + t < cnt) { if (W) s += x[t] * sb_rl(wl, q + t); else s += x[t]; }
+            }
+            sb_store(P, R, r, s);
+        }
+    }
+}
+// 220 / 221: for every member of a, the row of the matrix its residue picks, gathered by b's residues.  b's residues stay in
+// registers when one chunk holds them; a longer column is re-read chunk by chunk (two waits per SB_CR elements).
+template <bool W>
+__device__ __forceinline__ void sb_by_both(const DevProb &P, const SimRows &R)
+{
+    const DevSide &a = P.a, &b = P.b;
+    const bool held = b.many <= SB_CR;
+    unsigned cr[SB_CR / 4];
+    double wl = 0;
+    sb_col_res(b, R, 0, sb_min(SB_CR, b.many), cr);
+    if (W) wl = sb_lane_w(b.weight, R, 0, sb_min(SB_CR, b.many));
+    for (int r = R.r0; r < R.rows; r += R.rstep) {
+        const int m = R.m0 + r;
+        if (m >= a.right) break;
+        double s = 0;
+        SB_KEEP(wl);
+        for (int i0 = 0; i0 < a.many; i0 += 64) {
+            const int icnt = sb_min(64, a.many - i0);
+            const int ar = ((sb_bp) a.seq)[(size_t) (m + 1) * a.many + i0 + sb_min(R.lane, icnt - 1)];
+            const double wal = W ? sb_lane_w(a.weight, R, i0, icnt) : 0;
+            for (int i = 0; i < icnt; ++i) {
+                const sb_dp base = (sb_dp) P.simmtx + (size_t) __builtin_amdgcn_readlane(ar, i) * P.simdim;
+                double st = W ? 0 : s;
+                for (int j0 = 0; j0 < b.many; j0 += SB_CR) {
+                    const int cnt = sb_min(SB_CR, b.many - j0);
+                    if (!held) { sb_col_res(b, R, j0, cnt, cr); if (W) wl = sb_lane_w(b.weight, R, j0, cnt); }
+                    st = sb_gather<W>(base, cr, wl, cnt, st);
+                }
+                if (W) s += st * sb_rl(wal, i); else s = st;
+            }
+        }
+        sb_store(P, R, r, s);
+    }
+}
+// 33 / 330 (DC: a's entries decompacted, mseq.h:41): b's vector entries in registers, a row's one row ahead with a lane per entry
+template <bool DC>
+__device__ __forceinline__ void sb_by_vec(const DevProb &P, const SimRows &R)
+{
+    const DevSide &a = P.a, &b = P.b;
+    const sb_dp vb = (sb_dp) b.pseq + (size_t) (R.nn + 1) * b.nelm;
+    for (int j0 = 0; j0 < b.felm; j0 += G2G_SIMBLK_VC) {
+        const int cnt = sb_min(G2G_SIMBLK_VC, b.felm - j0);
+        double y[G2G_SIMBLK_VC];
+#pragma unroll
+        for (int t = 0; t < G2G_SIMBLK_VC; ++t) y[t] = vb[j0 + sb_min(t, cnt - 1)];
+        int lj = j0 + sb_min(R.lane, cnt - 1);
+        if (DC) lj = lj < 4 ? lj : lj == 4 ? 5 : 9;
+        double va_nx = ((sb_dp) a.pseq + (size_t) (sb_min(R.m0 + R.r0, a.right - 1) + 1) * a.nelm + a.felm)[lj];
+        for (int r = R.r0; r < R.rows; r += R.rstep) {
+            const int m = R.m0 + r;
+            if (m >= a.right) break;
+            const double va = va_nx;
+            va_nx = ((sb_dp) a.pseq + (size_t) (sb_min(m + R.rstep, a.right - 1) + 1) * a.nelm + a.felm)[lj];
+            double s = 0;
+            if (j0) s = R.dst[r * 64];
+#pragma unroll
+            for (int t = 0; t < G2G_SIMBLK_VC; ++t)
+                if (t < cnt) s += sb_rl(va, t) * y[t];
+            sb_store(P, R, r, s);
+        }
+    }
+}
+// 0, 11, 13, 31: one entry per cell
+__device__ __forceinline__ void sb_by_one(const DevProb &P, const SimRows &R, const int kind)
+{
+    const DevSide &a = P.a, &b = P.b;
+    const int ar0 = (kind == 11 || kind == 13) ? sb_rows_res0(P, R) : 0;
+    const int br0 = (kind == 11 || kind == 31) ? ((sb_bp) b.seq)[(size_t) (R.nn + 1) * b.many] : 0;
+    const sb_dp vb = (sb_dp) b.pseq + (size_t) (R.nn + 1) * b.nelm + b.felm;
+    for (int r = R.r0; r < R.rows; r += R.rstep) {
+        const int m = R.m0 + r;
+        if (m >= a.right) break;
+        const int ar = __builtin_amdgcn_readlane(ar0, r);
+        double s = 0;
+        if (kind == 11) s = ((sb_dp) P.simmtx)[(size_t) ar * P.simdim + br0];
+        else if (kind == 13) s = vb[ar];
+        else if (kind == 31) s = ((sb_dp) a.pseq + (size_t) (m + 1) * a.nelm + a.felm)[br0];
+        sb_store(P, R, r, s);
+    }
+}
+__device__ __forceinline__ void sim2_block(const DevProb &P, const SimRows &R)
+{
+    switch (P.sim2_kind) {
+    case 120: sb_by_colres<true, false>(P, R); break;
+    case 121: sb_by_colres<true, true>(P, R); break;
+    case 320: sb_by_colres<false, false>(P, R); break;
+    case 321: sb_by_colres<false, true>(P, R); break;
+    case 210: sb_by_rowres<true, false>(P, R); break;
+    case 211: sb_by_rowres<true, true>(P, R); break;
+    case 230: sb_by_rowres<false, false>(P, R); break;
+    case 231: sb_by_rowres<false, true>(P, R); break;
+    case 220: sb_by_both<false>(P, R); break;
+    case 221: sb_by_both<true>(P, R); break;
+    case 33: sb_by_vec<false>(P, R); break;
+    case 330: sb_by_vec<true>(P, R); break;
+    case 11: sb_by_one(P, R, 11); break;
+    case 13: sb_by_one(P, R, 13); break;
+    case 31: sb_by_one(P, R, 31); break;
+    default: sb_by_one(P, R, 0); break;
+    }
+}
+
 // unp1, maln.h:185-187
 __device__ __forceinline__ double unpa(const DevProb &P, int m, int n) { return thk_at(P.a, m)[0] * thk_at(P.b, n)[2] * -P.u; }
 __device__ __forceinline__ double unpb(const DevProb &P, int n, int m) { return thk_at(P.b, n)[0] * thk_at(P.a, m)[2] * -P.u; }

@@ -699,8 +699,6 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
     const double a_efq = row_ok ? thk_at(a, m)[2] : 0;
     const double pua_row = row_ok ? unpa(P, m, nlo) : 0;                 // fwd2c.h:380 (402 when a.inex.nils)
     SimBlk SB; SB.buf = (GLBV3 double *) simscr; SB.cbase = cbase;      // strip-local column scores (g2g_strip.h)
-    simblk_fill(P, SB, 0, m0, lane);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     double sim_cur = 0, bc_cur = 0;
     int os_cur = 0, oe_cur = 0, ot_cur = 0, te_cur = 0;       // starts / ends (pool positions) of the column's s and t lists
     bool have = false;
@@ -757,7 +755,8 @@ __device__ __forceinline__ void v6_strip(const DevProb &Pmem, lchar *lds, const 
         if (wr_rows && s > 0) flush_rows(n0 - 1 - llast);
         if (prog_self && s > 0 && (s & (pint - 1)) == 0) strip_publish<V6Strip>(S, n0 - llast);
         if ((s & (V6_FEED - 1)) == 0) { V6_MARK(2) refill(n0); team_sync(); }
-        if ((s & 63) == 0) { V6_MARK(3) simblk_fill(P, SB, (s >> 6) + 1, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+        // (the block of step 0 is made here too, in front of the first read: ONE inlined copy of the block scorer in the kernel)
+        if ((s & 63) == 0) { V6_MARK(3) for (int bk = s ? (s >> 6) + 1 : 0; bk <= (s >> 6) + 1; ++bk) simblk_fill_block(P, SB, bk, m0, lane); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         // -- hand-over from the row above
         hd = hu;
         hu = rs_up(oH); gu = rs_up(oG);

@@ -297,6 +297,26 @@ __device__ __forceinline__ void simblk_fill(const DevProb &P, const SimBlk &S, c
         if (n >= nlo && n < nhi) dst[r * 64] = sim2(P, m, n);
     }
 }
+// The same block through the block scorer (sim2_block, g2g_kernels.hip): one scorer dispatch per block, the column's operands
+// in registers, one memory wait per row or per eight elements instead of one or two per element.  v6 fills its blocks with it
+// (one wave per SIMD: nobody hides a wait).  The other strip families stay on simblk_fill: with the block scorer inlined their
+// register allocation loses more than the fill gains (scratch of g2g_v3r_hf2 256 -> 304 B, of g2g_v2_hf3 8 -> 1120 B, and
+// g2g_v3r_hf2, whose sweep DPs read sim31 in place and never fill a block, 134.5 -> 143.7 ms per sweep).
+__device__ __forceinline__ void simblk_fill_block(const DevProb &P, const SimBlk &S, const int bk, const int m0, const int tid,
+                                                  const int nthr = 64, const int rows = 64)
+{
+    const int n0 = S.cbase + bk * 64;
+    if (bk < 0 || n0 >= P.b.right) return;                 // (the whole block: every wave takes the same way)
+    SimRows R;                                             // sim2_block (g2g_kernels.hip): one scorer dispatch per block, all lanes active
+    R.lane = tid & 63;
+    asm volatile("" : "+v"(R.lane));                       // (nothing derived from the lane is hoisted out of the step loop into registers the cell needs)
+    R.n = n0 + R.lane; R.nn = R.n < P.b.right ? R.n : P.b.right - 1;
+    R.dst = S.buf + (size_t) (bk % 3) * 4096 + R.lane;
+    R.m0 = m0;
+    asm volatile("" : "+s"(R.m0));                         // (... nor anything derived from the strip's first row into SGPRs: g2g_v6_pf3 has neither to spare)
+    R.r0 = __builtin_amdgcn_readfirstlane(tid >> 6); R.rstep = nthr >> 6; R.rows = rows;
+    sim2_block(P, R);
+}
 __device__ __forceinline__ const GLBV3 double *simblk_at(const SimBlk &S, const int row, const int n)
 {
     const int k = n - S.cbase;
