@@ -473,7 +473,8 @@ int        g2g_alignb_ng_batch(g2g_ctx *ctx, const g2g_params *prm, int nseq, co
  * Limits (else G2G_ERR_ARG): k 1 .. 6 for protein, 1 .. 15 for DNA (beyond them the reference's 32-bit (queue * nalpha + c) % TabSize,
  * bitpat.cc:183, no longer forms the true words); measure -1 .. 6; reserved 0; 2 <= nseq, and nseq <= 4096 in the all-pairs form;
  * at most 16384 word positions ((right - left) - 2 k + 1) per sequence -- g2g_last_error names the sequence; 0 <= left <= right <= len.
- * Not on this path: reduced alphabets, spaced seeds, profiles of groups (many > 1), corr_mhits != 0.
+ * Not on this entry: reduced alphabets and spaced seeds -- g2g_kmer_dist_batch_spec below has them.  On neither: profiles of
+ * groups (many > 1), reading frames, corr_mhits != 0.
  * (Entry points added without a change of g2g_abi_version.) */
 typedef struct g2g_kmer_params {
     int32_t molc;      /* 1 PROTEIN, 2 DNA */
@@ -488,6 +489,37 @@ int        g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int nseq
                                int npairs, const int32_t *ia, const int32_t *ib, double *dist, int32_t *counts);
 /* host only, no context: the closed form from the three integers of each pair */
 int        g2g_kmer_dist_from_counts(const g2g_kmer_params *kp, int npairs, const int32_t *counts, double *dist);
+
+/* ---- the same with a residue classification and a seed: all three inputs of setqdiv(k, ap, bp, dm) (qdiv.cc:36-43) -------
+ *   classes : classes[code] is the class of a residue code (what ReducWord builds from a pattern such as A|C|D|EQ|FY|...,
+ *             src/bitpat.cc:59-95; the caller supplies the table, none is built in).  A class >= nalpha -- 0xFF is one -- and a
+ *             code >= nclasses break a word at the positions the seed examines.  Words are base-nalpha numbers of classes.
+ *   seed    : NULL: the continuous seed of k, as above with base nalpha -- (right - left) - 2 k + 1 word positions.  Else a string
+ *             of '1' / '0' (Bitpat::Bitpat, Bitpat_wq::word / flaw, bitpat.cc:99-131, 168-202), width = its length, weight = its
+ *             number of '1's: the scan reads the residues left .. right - width - 1; after residue p >= left + width - 1 the word is
+ *             formed of the classes at p - width + 1 + o for the offsets o of the '1's, left to right, and counted iff each of them is
+ *             < nalpha (a bad residue under a '0' breaks nothing): (right - left) - 2 width + 1 word positions.  An all-ones seed gives
+ *             the continuous result.
+ *   pair    : as above, with the row of qdiv's param (qdiv.cc:181-186, 214-222) chosen by nalpha as given and by k, also where a seed
+ *             string is given: nalpha 14 with k 3 / 4 / 5 -> (0.92042, 0.18677) / (0.34576, 0.07108) / (0.22333, 0.03164), every other
+ *             case (0.18704, 0.00501).
+ * Limits (else G2G_ERR_ARG, before the device is asked for): nalpha 0 (= 20 / 4) or 2 .. 20 (protein) / 2 .. 4 (DNA), and the full
+ * alphabet where classes is NULL; nclasses 1 .. 256; k 1 .. 15 (0: the default, 5 / 10); without a seed string
+ * nalpha^(k + 1) <= 2^32 (beyond it the reference's 32-bit queue no longer holds the true words); a seed string of '0' / '1' only,
+ * first and last character '1', width <= 32, weight 1 .. 15, nalpha^weight < 2^32; reserved 0; at most 16384 word positions per
+ * sequence, counted with the width; the rest as for g2g_kmer_dist_batch.  Not on this path: groups (many > 1), reading frames,
+ * corr_mhits != 0, and the reference's own alphabet tables (for protein with Nalpha 6 .. 20 it ignores a caller's pattern).
+ * With nalpha 0, classes NULL and seed NULL both functions return what g2g_kmer_dist_batch / g2g_kmer_dist_from_counts return. */
+typedef struct g2g_kmer_spec {
+    int32_t molc, k, measure, nalpha;   /* k 0 / measure -1 / nalpha 0: the defaults */
+    const uint8_t *classes;             /* classes[code], code < nclasses; NULL: the full alphabet of g2g_kmer_dist_batch */
+    int32_t nclasses, reserved;         /* reserved 0 */
+    const char *seed;                   /* NULL: continuous seed of k */
+} g2g_kmer_spec;
+int        g2g_kmer_dist_batch_spec(g2g_ctx *ctx, const g2g_kmer_spec *sp, int nseq, const g2g_dseq *seqs,
+                                    int npairs, const int32_t *ia, const int32_t *ib, double *dist, int32_t *counts);
+/* host only, no context; classes and nclasses are not looked at */
+int        g2g_kmer_dist_from_counts_spec(const g2g_kmer_spec *sp, int npairs, const int32_t *counts, double *dist);
 
 #ifdef __cplusplus
 }

@@ -89,7 +89,13 @@ class KmerParams(C.Structure):
     _fields_ = [("molc", C.c_int32), ("k", C.c_int32), ("measure", C.c_int32), ("reserved", C.c_int32)]
 
 
-EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32))
+class KmerSpec(C.Structure):
+    """g2g_kmer_spec: g2g_kmer_params with the alphabet size, a class table (classes[code]) and a seed string"""
+    _fields_ = [("molc", C.c_int32), ("k", C.c_int32), ("measure", C.c_int32), ("nalpha", C.c_int32), ("classes", c_u8p),
+                ("nclasses", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_char_p)]
+
+
+EXCHANGE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32))
 
 
 SCORE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(Skl)), C.POINTER(C.c_int),

@@ -88,6 +88,9 @@ def lib():
     L.g2g_kmer_dist_batch.argtypes = [C.c_void_p, C.POINTER(_abi.KmerParams), C.c_int, C.POINTER(_abi.DSeq), C.c_int,
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _abi.c_f64p, C.POINTER(C.c_int32)]
     L.g2g_kmer_dist_from_counts.argtypes = [C.POINTER(_abi.KmerParams), C.c_int, C.POINTER(C.c_int32), _abi.c_f64p]
+    L.g2g_kmer_dist_batch_spec.argtypes = [C.c_void_p, C.POINTER(_abi.KmerSpec), C.c_int, C.POINTER(_abi.DSeq), C.c_int,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), _abi.c_f64p, C.POINTER(C.c_int32)]
+    L.g2g_kmer_dist_from_counts_spec.argtypes = [C.POINTER(_abi.KmerSpec), C.c_int, C.POINTER(C.c_int32), _abi.c_f64p]
     bind_level1(L)
     _lib = L
     return L

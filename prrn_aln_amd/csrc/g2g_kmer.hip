@@ -23,6 +23,9 @@
 //       network sorts the power-of-two array in LDS; a run head finds its count by an upper-bound search in the sorted array and
 //       its place in the list by a workgroup prefix sum.  Lists lie in HBM at a fixed stride per sequence (its number of word
 //       positions, known to the host), keys and counts in two arrays.
+//   g2g_kmer_profile_spec_kernel   the same for g2g_kmer_dist_batch_spec: a caller's class table (staged in LDS) instead of the full
+//       alphabet, base nalpha, and a seed -- a word position reads its digits at the offsets of the seed's '1's (one 32-bit mask,
+//       a kernel argument; the continuous seed of k is the k low bits).  Sort, compaction and lists are the same.
 //   g2g_kmer_allpairs_kernel   a workgroup keeps the list of member j in LDS and takes up to KM_CHUNK partners i < j, one partner
 //       per wave at a time: each lane loads consecutive entries of the partner's list (coalesced), binary-searches its key in
 //       LDS and adds the smaller count; the wave reduces with shuffles and lane 0 stores.  Results of a workgroup are consecutive
@@ -133,6 +136,111 @@ extern "C" __global__ void __launch_bounds__(KM_THREADS) g2g_kmer_profile_kernel
     }
 }
 
+// The second half of g2g_kmer_profile_kernel, word for word, for the kernel below: the N keys in LDS (a power of two; KM_NOWORD
+// behind the words) are sorted, the run heads become this sequence's (word, count) list, meta = (Unq, T).  The whole workgroup
+// calls it, after the barrier behind the last key written.  (g2g_kmer_profile_kernel keeps its own copy: routed through this
+// function its code object came out a few instructions different, and g2g_kmer_dist_batch is to stay as measured.)
+__device__ __forceinline__ void km_sort_emit(unsigned *key, int *wsum, const int N, const KmSeq sq, unsigned *keys, int *cnts, int2 *meta)
+{
+    const int tid = threadIdx.x;
+    for (int size = 2; size <= N; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (N >> 1); t += KM_THREADS) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const unsigned a = key[i], b = key[j];
+                if ((a > b) == ((i & size) == 0)) { key[i] = b; key[j] = a; }
+            }
+            __syncthreads();
+        }
+    // run heads: thread t looks at the E consecutive entries from t * E
+    const int E = N > KM_THREADS ? N / KM_THREADS : 1, base = tid * E;
+    int c = 0;
+    if (base < N)
+        for (int e = 0; e < E; ++e) {
+            const int i = base + e;
+            const unsigned v = key[i];
+            c += v != KM_NOWORD && (i == 0 || key[i - 1] != v);
+        }
+    const int lane = tid & 63, wave = tid >> 6;
+    int inc = c;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += y;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int o = inc - c;
+    for (int w = 0; w < wave; ++w) o += wsum[w];
+    if (base < N)
+        for (int e = 0; e < E; ++e) {
+            const int i = base + e;
+            const unsigned v = key[i];
+            if (v != KM_NOWORD && (i == 0 || key[i - 1] != v)) {
+                int lo = i + 1, n = N - lo;                           // the first entry above v
+                while (n > 0) {
+                    const int half = n >> 1;
+                    if (key[lo + half] <= v) { lo += half + 1; n -= half + 1; } else n = half;
+                }
+                keys[sq.list + o] = v;                                // o < Unq <= W: inside this sequence's stride
+                cnts[sq.list + o] = lo - i;
+                ++o;
+            }
+        }
+    if (tid == 0) {
+        int unq = 0;
+        for (int w = 0; w < KM_THREADS / 64; ++w) unq += wsum[w];
+        int lo = 0, n = N;                                            // T: the first KM_NOWORD
+        while (n > 0) {
+            const int half = n >> 1;
+            if (key[lo + half] != KM_NOWORD) { lo += half + 1; n -= half + 1; } else n = half;
+        }
+        meta[blockIdx.x] = make_int2(unq, lo);
+    }
+}
+
+// The general case (g2g_kmer_dist_batch_spec): a caller's class table and a seed.  seed: bit o is set where the seed string has a
+// '1' at offset o (width <= 32; the continuous seed of k is the k low bits), so the offsets are wave-uniform and need no table.
+// sq.words counts with the width: (right - left) - 2 width + 1, and the word at position p examines the digits p + o.
+extern "C" __global__ void __launch_bounds__(KM_THREADS) g2g_kmer_profile_spec_kernel(const uint8_t *pool, const KmSeq *seqs, const uint8_t *classes,
+                                                                                      const unsigned nalpha, const int width, const unsigned seed,
+                                                                                      unsigned *keys, int *cnts, int2 *meta)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char km_lds[];
+    const int tid = threadIdx.x;
+    const KmSeq sq = seqs[blockIdx.x];
+    const int W = sq.words;
+    if (W <= 0) {                                                     // (the whole workgroup: no barrier is skipped by a part of it)
+        if (tid == 0) meta[blockIdx.x] = make_int2(0, 0);
+        return;
+    }
+    int N = 2;
+    while (N < W) N <<= 1;
+    unsigned *key = (unsigned *) km_lds;                              // N keys | 32 wave sums | 256 B class table | W + width - 1 digits
+    int *wsum = (int *) (key + N);
+    unsigned char *tab = (unsigned char *) (wsum + 32);
+    unsigned char *dig = tab + 256;
+    if (tid < 256) tab[tid] = classes[tid];
+    __syncthreads();
+    const int nres = W + width - 1;
+    for (int i = tid; i < nres; i += KM_THREADS) {
+        const unsigned c = tab[pool[sq.res + i]];
+        dig[i] = (unsigned char) (c < nalpha ? c : 0xFFu);             // a class >= nalpha breaks the word where the seed examines it
+    }
+    __syncthreads();
+    for (int p = tid; p < N; p += KM_THREADS) {
+        unsigned w = 0, bad = p < W ? 0u : 1u;
+        if (!bad)
+            for (unsigned m = seed; m; m &= m - 1) {                  // the '1's left to right
+                const unsigned d = dig[p + __ffs(m) - 1];
+                bad |= d >> 7;
+                w = w * nalpha + d;
+            }
+        key[p] = bad ? KM_NOWORD : w;
+    }
+    __syncthreads();
+    km_sort_emit(key, wsum, N, sq, keys, cnts, meta);
+}
+
 // sum over the words of B that A holds of min(count_A, count_B), by one wave; the same value in every lane
 __device__ __forceinline__ int km_wave_shared(const unsigned *ak, const int *ac, const int na, const unsigned *bk, const int *bc, const int nb, const int lane)
 {
@@ -213,10 +321,25 @@ double km_pamcorrect(double x)                                        // divseq.
     if (x <= 0) return (0);
     return (100. * x);
 }
-// qdiv, qdiv.cc:202-231, with many == 1 on both sides and Nalpha != 14 (the d420 row of param)
-double km_qdiv(const int s, const int ta, const int tb, const int measure)
+void km_error(const char *who, const char *msg)
 {
-    const double p0 = 0.18704, p1 = 0.00501;
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", who, msg);
+    g2g_set_error("%s", buf);
+}
+// what both entries come down to.  width / seed: the seed (bit o: a '1' at offset o; the continuous seed of k is its k low bits);
+// p0, p1: the row of qdiv's param; classes: only where spec (the spec entry's profile kernel)
+struct KmPlan { int molc, k, measure, width; unsigned nalpha, seed; double p0, p1; bool spec; uint8_t classes[256]; };
+// the row of param (qdiv.cc:181-186, 214-222): by Nalpha as given and by Ktuple, whatever the seed
+void km_row(KmPlan &pl)
+{
+    static const double param[4][2] = {{0.92042, 0.18677}, {0.34576, 0.07108}, {0.22333, 0.03164}, {0.18704, 0.00501}};   // d314 d414 d514 d420
+    const int r = pl.nalpha == 14 && pl.k >= 3 && pl.k <= 5 ? pl.k - 3 : 3;
+    pl.p0 = param[r][0]; pl.p1 = param[r][1];
+}
+// qdiv, qdiv.cc:202-231, with many == 1 on both sides
+double km_qdiv(const int s, const int ta, const int tb, const int measure, const double p0, const double p1)
+{
     double f = (double) ta;                                           // TtlKmers / many, exact
     const double e = (double) tb;
     f = f < e ? f : e;                                                // min(f, e) * a->many * b->many
@@ -241,43 +364,122 @@ double km_qdiv(const int s, const int ta, const int tb, const int measure)
 // the parameters taken literally (resetqdiv's swapping of one molecule's defaults for the other's, qdiv.cc:45-57, is not reproduced).
 // k: the reference forms (queue * nalpha + c) % TabSize in 32-bit unsigned arithmetic (bitpat.cc:183), so its words are the true
 // words only while Nalpha^(k + 1) <= 2^32: protein k <= 6, DNA k <= 15 (MaxBitPat = 16 bounds k as well)
-bool km_params(const char *who, const g2g_kmer_params *kp, int &k, int &measure)
+bool km_params(const char *who, const g2g_kmer_params *kp, KmPlan &pl)
 {
     if (!kp) { g2g_set_error("%s: no parameters", who); return false; }
     if (kp->molc != 1 && kp->molc != 2) { g2g_set_error("%s: molc is 1 (protein) or 2 (DNA)", who); return false; }
-    k = kp->k ? kp->k : kp->molc == 1 ? 5 : 10;                       // def_wcp_aa / def_wcp_nc, qdiv.cc:32-33
-    measure = kp->measure != -1 ? kp->measure : kp->molc == 1 ? KM_Qpamd : KM_QJuCa;
+    const int k = kp->k ? kp->k : kp->molc == 1 ? 5 : 10;             // def_wcp_aa / def_wcp_nc, qdiv.cc:32-33
+    const int measure = kp->measure != -1 ? kp->measure : kp->molc == 1 ? KM_Qpamd : KM_QJuCa;
     if (k < 1 || k > (kp->molc == 1 ? 6 : 15)) { g2g_set_error("%s: k outside 1 .. 6 (protein) / 1 .. 15 (DNA)", who); return false; }
     if (measure < 0 || measure > 6) { g2g_set_error("%s: measure outside -1 .. 6", who); return false; }
     if (kp->reserved) { g2g_set_error("%s: reserved is not 0 (reduced alphabets and spaced seeds are not on this path)", who); return false; }
+    pl.molc = kp->molc; pl.k = pl.width = k; pl.measure = measure;
+    pl.nalpha = kp->molc == 1 ? 20u : 4u; pl.seed = (1u << k) - 1u; pl.spec = false;
+    km_row(pl);
     return true;
 }
-}
-
-extern "C" int g2g_kmer_dist_from_counts(const g2g_kmer_params *kp, int npairs, const int32_t *counts, double *dist)
+// g2g_kmer_spec.  The words must be the true ones: the reference's continuous queue is (queue * nalpha + c) % nalpha^k in 32 bits
+// (bitpat.cc:183), its spaced word a plain 32-bit sum (bitpat.cc:191-199), and KM_NOWORD must stay no word.  The batch entry wants
+// the classes too; the closed form does not look at them.
+bool km_spec(const char *who, const g2g_kmer_spec *sp, const bool batch, KmPlan &pl)
 {
-    int k = 0, measure = 0;
-    if (!km_params("g2g_kmer_dist_from_counts", kp, k, measure)) return G2G_ERR_ARG;
-    if (npairs < 0 || (npairs && (!counts || !dist))) { g2g_set_error("%s", "g2g_kmer_dist_from_counts: bad argument"); return G2G_ERR_ARG; }
+    if (!sp) { g2g_set_error("%s: no parameters", who); return false; }
+    if (sp->molc != 1 && sp->molc != 2) { g2g_set_error("%s: molc is 1 (protein) or 2 (DNA)", who); return false; }
+    const int full = sp->molc == 1 ? 20 : 4;
+    const int k = sp->k ? sp->k : sp->molc == 1 ? 5 : 10;
+    const int measure = sp->measure != -1 ? sp->measure : sp->molc == 1 ? KM_Qpamd : KM_QJuCa;
+    const int nalpha = sp->nalpha ? sp->nalpha : full;
+    if (nalpha < 2 || nalpha > full) { g2g_set_error("%s: nalpha is 0 or 2 .. 20 (protein) / 2 .. 4 (DNA)", who); return false; }
+    if (k < 1 || k > 15) { g2g_set_error("%s: k outside 1 .. 15", who); return false; }
+    if (measure < 0 || measure > 6) { g2g_set_error("%s: measure outside -1 .. 6", who); return false; }
+    if (sp->reserved) { g2g_set_error("%s: reserved is not 0", who); return false; }
+    int width = k, weight = k;
+    unsigned seed = (1u << k) - 1u;
+    if (sp->seed) {
+        const size_t n = strlen(sp->seed);
+        if (n < 1 || n > 32) { g2g_set_error("%s: seed: a string of 1 .. 32 characters '0' / '1'", who); return false; }
+        width = (int) n; weight = 0; seed = 0;
+        for (int o = 0; o < width; ++o) {
+            if (sp->seed[o] != '0' && sp->seed[o] != '1') { g2g_set_error("%s: seed: only '0' and '1'", who); return false; }
+            if (sp->seed[o] == '1') { seed |= 1u << o; ++weight; }
+        }
+        if (sp->seed[0] != '1' || sp->seed[width - 1] != '1') { g2g_set_error("%s: seed: the first and the last character are '1'", who); return false; }
+        if (weight > 15) { g2g_set_error("%s: seed: weight above 15", who); return false; }
+    }
+    unsigned long long tab = 1;                                       // continuous: nalpha^(k + 1) <= 2^32; seed string: nalpha^weight < 2^32
+    for (int q = 0; q < (sp->seed ? weight : k + 1) && tab <= (1ULL << 32); ++q) tab *= (unsigned) nalpha;
+    if (sp->seed ? tab >= (1ULL << 32) : tab > (1ULL << 32)) {
+        if (sp->seed) g2g_set_error("%s: seed: nalpha^weight is not below 2^32", who);
+        else g2g_set_error("%s: k: nalpha^(k + 1) is above 2^32", who);
+        return false;
+    }
+    pl.molc = sp->molc; pl.k = k; pl.measure = measure; pl.width = width; pl.nalpha = (unsigned) nalpha; pl.seed = seed; pl.spec = true;
+    km_row(pl);
+    if (!batch) return true;
+    if (!sp->classes) {
+        if (nalpha != full) { g2g_set_error("%s: an nalpha below the full alphabet needs classes", who); return false; }
+        for (unsigned c = 0; c < 256; ++c)                              // the full alphabet: ALA 3 .. VAL 22 (src/cmn.h:111-114); A C G T
+            pl.classes[c] = sp->molc == 1 ? (c - 3u < 20u ? c - 3u : 0xFFu) : c == 2u ? 0u : c == 3u ? 1u : c == 5u ? 2u : c == 9u ? 3u : 0xFFu;
+        return true;
+    }
+    if (sp->nclasses < 1 || sp->nclasses > 256) { g2g_set_error("%s: nclasses outside 1 .. 256", who); return false; }
+    memset(pl.classes, 0xFF, sizeof pl.classes);                      // codes >= nclasses break the word
+    memcpy(pl.classes, sp->classes, (size_t) sp->nclasses);
+    return true;
+}
+int km_from_counts(const char *who, const KmPlan &pl, int npairs, const int32_t *counts, double *dist)
+{
+    if (npairs < 0 || (npairs && (!counts || !dist))) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
     for (int p = 0; p < npairs; ++p) {
         const int32_t *c = counts + 3 * (size_t) p;
         if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] > (c[1] < c[2] ? c[1] : c[2])) {
             char msg[96];
             snprintf(msg, sizeof msg, "pair %d: counts %d %d %d are no s <= min(Ta, Tb)", p, c[0], c[1], c[2]);
-            g2g_set_error("g2g_kmer_dist_from_counts: %s", msg);
+            km_error(who, msg);
             return G2G_ERR_ARG;
         }
-        dist[p] = 100. * km_qdiv(c[0], c[1], c[2], measure);           // kcmp_main, qdiv.cc:239
+        dist[p] = 100. * km_qdiv(c[0], c[1], c[2], pl.measure, pl.p0, pl.p1);   // kcmp_main, qdiv.cc:239
     }
     return G2G_OK;
+}
+int km_batch(const char *who, g2g_ctx *ctx, const KmPlan &pl, int nseq, const g2g_dseq *seqs, int npairs, const int32_t *ia, const int32_t *ib,
+             double *dist, int32_t *counts);
+}
+
+extern "C" int g2g_kmer_dist_from_counts(const g2g_kmer_params *kp, int npairs, const int32_t *counts, double *dist)
+{
+    KmPlan pl;
+    if (!km_params("g2g_kmer_dist_from_counts", kp, pl)) return G2G_ERR_ARG;
+    return km_from_counts("g2g_kmer_dist_from_counts", pl, npairs, counts, dist);
+}
+
+extern "C" int g2g_kmer_dist_from_counts_spec(const g2g_kmer_spec *sp, int npairs, const int32_t *counts, double *dist)
+{
+    KmPlan pl;
+    if (!km_spec("g2g_kmer_dist_from_counts_spec", sp, false, pl)) return G2G_ERR_ARG;
+    return km_from_counts("g2g_kmer_dist_from_counts_spec", pl, npairs, counts, dist);
 }
 
 extern "C" int g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int nseq, const g2g_dseq *seqs, int npairs,
                                    const int32_t *ia, const int32_t *ib, double *dist, int32_t *counts)
 {
-    const char *who = "g2g_kmer_dist_batch";
-    int k = 0, measure = 0;
-    if (!km_params(who, kp, k, measure)) return G2G_ERR_ARG;
+    KmPlan pl;
+    if (!km_params("g2g_kmer_dist_batch", kp, pl)) return G2G_ERR_ARG;
+    return km_batch("g2g_kmer_dist_batch", ctx, pl, nseq, seqs, npairs, ia, ib, dist, counts);
+}
+
+extern "C" int g2g_kmer_dist_batch_spec(g2g_ctx *ctx, const g2g_kmer_spec *sp, int nseq, const g2g_dseq *seqs, int npairs,
+                                        const int32_t *ia, const int32_t *ib, double *dist, int32_t *counts)
+{
+    KmPlan pl;
+    if (!km_spec("g2g_kmer_dist_batch_spec", sp, true, pl)) return G2G_ERR_ARG;
+    return km_batch("g2g_kmer_dist_batch_spec", ctx, pl, nseq, seqs, npairs, ia, ib, dist, counts);
+}
+
+namespace {
+int km_batch(const char *who, g2g_ctx *ctx, const KmPlan &pl, int nseq, const g2g_dseq *seqs, int npairs, const int32_t *ia, const int32_t *ib,
+             double *dist, int32_t *counts)
+{
     if (!seqs || !dist || (!ia) != (!ib)) { g2g_set_error("%s: null argument", who); return G2G_ERR_ARG; }
     const bool all = !ia;
     if (nseq < 2 || npairs < 0) { g2g_set_error("%s: nseq >= 2 and npairs >= 0", who); return G2G_ERR_ARG; }
@@ -290,7 +492,7 @@ extern "C" int g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int 
             if (ia[p] < 0 || ia[p] >= nseq || ib[p] < 0 || ib[p] >= nseq) {
                 char msg[96];
                 snprintf(msg, sizeof msg, "pair %d: index %d or %d outside 0 .. %d", p, ia[p], ib[p], nseq - 1);
-                g2g_set_error("g2g_kmer_dist_batch: %s", msg);
+                km_error(who, msg);
                 return G2G_ERR_ARG;
             }
     // the pool holds each sequence's window, left .. right - 1; the word positions give the list strides
@@ -302,13 +504,13 @@ extern "C" int g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int 
         char msg[128];
         if ((!s.res && s.right > s.left) || s.left < 0 || s.right < s.left || s.right > s.len) {
             snprintf(msg, sizeof msg, "sequence %d: no residues, or not 0 <= left <= right <= len", i);
-            g2g_set_error("g2g_kmer_dist_batch: %s", msg);
+            km_error(who, msg);
             return G2G_ERR_ARG;
         }
-        const long long w = std::max(0LL, (long long) (s.right - s.left) - 2 * k + 1);
+        const long long w = std::max(0LL, (long long) (s.right - s.left) - 2 * pl.width + 1);
         if (w > G2G_KMER_MAX_WINDOW) {
             snprintf(msg, sizeof msg, "sequence %d has %lld word positions, more than %d", i, w, G2G_KMER_MAX_WINDOW);
-            g2g_set_error("g2g_kmer_dist_batch: %s", msg);
+            km_error(who, msg);
             return G2G_ERR_ARG;
         }
         hs[i].res = (long long) pool; hs[i].list = (long long) lists; hs[i].words = (int) w; hs[i].pad = 0;
@@ -321,15 +523,16 @@ extern "C" int g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int 
     HIPCHK(hipSetDevice(ctx->device));
     if (npairs == 0) return G2G_OK;
     auto al = [](size_t v) { return (v + 255) & ~(size_t) 255; };
-    // device image: pool | seqs | ia | ib (uploaded) | keys | cnts | meta | out
+    // device image: pool | seqs | ia | ib | class table (uploaded) | keys | cnts | meta | out
     const size_t o_seq = al(pool), o_ia = al(o_seq + sizeof(KmSeq) * nseq), o_ib = al(o_ia + (all ? 0 : 4 * (size_t) npairs)),
-                 o_key = al(o_ib + (all ? 0 : 4 * (size_t) npairs)), o_cnt = al(o_key + 4 * lists), o_meta = al(o_cnt + 4 * lists),
+                 o_tab = al(o_ib + (all ? 0 : 4 * (size_t) npairs)), o_key = al(o_tab + (pl.spec ? sizeof pl.classes : 0)), o_cnt = al(o_key + 4 * lists), o_meta = al(o_cnt + 4 * lists),
                  o_out = al(o_meta + 8 * (size_t) nseq), total = o_out + 12 * (size_t) npairs;
     std::vector<char> img(o_key, 0);
     for (int i = 0; i < nseq; ++i)
         if (seqs[i].right > seqs[i].left) memcpy(img.data() + hs[i].res, seqs[i].res + seqs[i].left, (size_t) (seqs[i].right - seqs[i].left));
     memcpy(img.data() + o_seq, hs.data(), sizeof(KmSeq) * nseq);
     if (!all) { memcpy(img.data() + o_ia, ia, 4 * (size_t) npairs); memcpy(img.data() + o_ib, ib, 4 * (size_t) npairs); }
+    if (pl.spec) memcpy(img.data() + o_tab, pl.classes, sizeof pl.classes);
     std::vector<int32_t> own;
     if (!counts) { own.resize(3 * (size_t) npairs); counts = own.data(); }
     char *dev = 0;
@@ -344,11 +547,16 @@ extern "C" int g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int 
     if (e == hipSuccess) {
         int n2 = 2;
         while (n2 < wmax) n2 <<= 1;
-        const size_t lds = 4 * (size_t) n2 + 128 + (((size_t) wmax + k + 15) & ~(size_t) 15);
-        if (lds > 64 * 1024) e = hipFuncSetAttribute((const void *) g2g_kmer_profile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        const size_t lds = 4 * (size_t) n2 + 128 + (pl.spec ? sizeof pl.classes : 0) + (((size_t) wmax + pl.width + 15) & ~(size_t) 15);
+        const void *fn = pl.spec ? (const void *) g2g_kmer_profile_spec_kernel : (const void *) g2g_kmer_profile_kernel;
+        if (lds > 64 * 1024) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(g2g_kmer_profile_kernel, dim3(nseq), dim3(KM_THREADS), lds, ctx->stream, (const uint8_t *) dev, dseq, (int) kp->molc, k,
-                               dkey, dcnt, dmeta);
+            if (pl.spec)
+                hipLaunchKernelGGL(g2g_kmer_profile_spec_kernel, dim3(nseq), dim3(KM_THREADS), lds, ctx->stream, (const uint8_t *) dev, dseq,
+                                   (const uint8_t *) (dev + o_tab), pl.nalpha, pl.width, pl.seed, dkey, dcnt, dmeta);
+            else
+                hipLaunchKernelGGL(g2g_kmer_profile_kernel, dim3(nseq), dim3(KM_THREADS), lds, ctx->stream, (const uint8_t *) dev, dseq, pl.molc, pl.k,
+                                   dkey, dcnt, dmeta);
             e = hipGetLastError();
         }
     }
@@ -382,6 +590,7 @@ extern "C" int g2g_kmer_dist_batch(g2g_ctx *ctx, const g2g_kmer_params *kp, int 
         }
     }
     (void) hipFree(dev);
-    if (e != hipSuccess) { g2g_set_error("g2g_kmer_dist_batch: %s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
-    return g2g_kmer_dist_from_counts(kp, npairs, counts, dist);
+    if (e != hipSuccess) { km_error(who, hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
+    return km_from_counts(who, pl, npairs, counts, dist);
+}
 }

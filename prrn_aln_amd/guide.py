@@ -106,6 +106,11 @@ def kmer_distance(ctx, seqs: Sequence, molc: int, k: int = 0, measure: int = -1,
     the guide tree is KTree.from_dist(dist, with_weights=False)) or the index pairs (ia, ib).  k = 0 / measure = -1: the
     reference's defaults (protein k 5 with Qpamd, DNA k 10 with QJuCa).  A sequence is an array of residue codes, or a tuple
     (codes, left, right) for a range inside a longer buffer.  With want_counts: (dist, counts int32[npairs, 3] = s, Ta, Tb)."""
+    return _kmer_batch(lib().g2g_kmer_dist_batch, ctx, _kmer_params(molc, k, measure), seqs, ia, ib, want_counts)
+
+
+def _kmer_batch(entry, ctx, kp, seqs: Sequence, ia, ib, want_counts: bool):
+    """the call both k-mer entries share: entry is the library function, kp its parameter structure"""
     if (ia is None) != (ib is None):
         raise ValueError("ia and ib come together")
     ds = (_abi.DSeq * max(len(seqs), 1))()
@@ -128,12 +133,65 @@ def kmer_distance(ctx, seqs: Sequence, molc: int, k: int = 0, measure: int = -1,
         pa, pb = ia.ctypes.data_as(C.POINTER(C.c_int32)), ib.ctypes.data_as(C.POINTER(C.c_int32))
     dist = np.zeros(npairs, np.float64)
     counts = np.zeros((npairs, 3), np.int32)
-    kp = _kmer_params(molc, k, measure)
-    rc = lib().g2g_kmer_dist_batch(ctx._h, C.byref(kp), nseq, ds, npairs, pa, pb, dist.ctypes.data_as(_abi.c_f64p),
-                                   counts.ctypes.data_as(C.POINTER(C.c_int32)) if want_counts else None)
+    rc = entry(ctx._h, C.byref(kp), nseq, ds, npairs, pa, pb, dist.ctypes.data_as(_abi.c_f64p),
+               counts.ctypes.data_as(C.POINTER(C.c_int32)) if want_counts else None)
     if rc != 0:
-        raise G2GError("g2g_kmer_dist_batch rc=%d: %s" % (rc, last_error()))
+        raise G2GError("%s rc=%d: %s" % (entry.__name__, rc, last_error()))
     return (dist, counts) if want_counts else dist
+
+
+def kmer_classes(pattern: str, molc: int) -> np.ndarray:
+    """uint8[256] class table of a -A style classification such as "A|C|D|EQ|FY|..." (ReducWord::ReducWord, src/bitpat.cc:78-86):
+    every non-letter starts the next class; a letter's residue code (the encoding of operator.encode) gets the current class;
+    codes no letter names are 0xFF, which breaks a word.  No table is built in: the caller brings the pattern."""
+    from .operator import _AA, _NT, PROTEIN
+    enc = _AA if molc == PROTEIN else _NT
+    tab = np.full(256, 0xFF, np.uint8)
+    cls = 0
+    for ch in pattern:
+        if not ch.isalpha():
+            cls += 1
+        elif ch.upper() in enc:
+            if cls > 0xFF:
+                raise ValueError("more than 256 classes")
+            tab[enc[ch.upper()]] = cls
+    return tab
+
+
+def _kmer_spec(molc: int, k: int, measure: int, nalpha: int, classes, seed):
+    """(g2g_kmer_spec, what it points to)"""
+    sp = _abi.KmerSpec()
+    sp.molc, sp.k, sp.measure, sp.nalpha, sp.nclasses, sp.reserved = int(molc), int(k), int(measure), int(nalpha), 0, 0
+    tab = None
+    if classes is not None:
+        tab = kmer_classes(classes, molc) if isinstance(classes, str) else np.ascontiguousarray(classes, np.uint8)
+        if tab.ndim != 1 or not 1 <= len(tab) <= 256:
+            raise ValueError("classes: a pattern string or a table of 1 .. 256 entries")
+        sp.classes, sp.nclasses = tab.ctypes.data_as(_abi.c_u8p), len(tab)
+    sp.seed = None if seed is None else seed.encode()
+    return sp, tab
+
+
+def kmer_dist_from_counts_spec(counts: np.ndarray, molc: int, k: int = 0, measure: int = -1, nalpha: int = 0, seed=None) -> np.ndarray:
+    """g2g_kmer_dist_from_counts_spec (host only): kmer_dist_from_counts with the row of qdiv's fit parameters that belongs to
+    (nalpha, k) -- nalpha 14 with k 3 / 4 / 5 has its own; k counts, not the seed's weight"""
+    cnt = np.ascontiguousarray(counts, np.int32).reshape(-1, 3)
+    dist = np.zeros(len(cnt), np.float64)
+    sp, _ = _kmer_spec(molc, k, measure, nalpha, None, seed)
+    rc = lib().g2g_kmer_dist_from_counts_spec(C.byref(sp), len(cnt), cnt.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(_abi.c_f64p))
+    if rc != 0:
+        raise G2GError("g2g_kmer_dist_from_counts_spec rc=%d: %s" % (rc, last_error()))
+    return dist
+
+
+def kmer_distance_spec(ctx, seqs: Sequence, molc: int, k: int = 0, measure: int = -1, nalpha: int = 0, classes=None, seed=None,
+                       ia=None, ib=None, want_counts: bool = False):
+    """g2g_kmer_dist_batch_spec: kmer_distance over a reduced alphabet and / or under a spaced seed -- the reference's qdiv with
+    -R nalpha, -A classes and -B seed.  classes: a pattern string (kmer_classes) or a table classes[code]; a class >= nalpha breaks
+    a word.  seed: a string of '1' / '0' (first and last '1', width <= 32, weight <= 15), None for the continuous seed of k.  The
+    fit parameters go by (nalpha, k) even under a seed.  With the defaults it is kmer_distance."""
+    sp, keep = _kmer_spec(molc, k, measure, nalpha, classes, seed)
+    return _kmer_batch(lib().g2g_kmer_dist_batch_spec, ctx, sp, seqs, ia, ib, want_counts)
 
 
 def alignb_ng_batch(ctx, prm: "_abi.Params", seqs: Sequence[np.ndarray], ia: Sequence[int], ib: Sequence[int]):

@@ -8,10 +8,14 @@
                the closed forms on the host; wall clock, median of the same runs
   alnscored_ms guide.distance_matrix (one banded alnScoreD DP per pair, wall clock, second of two runs) -- 256 family only
 
+With --nalpha / --k / --seed the same shapes are timed again through g2g_kmer_dist_batch_spec (g2g_kmer_profile_spec_kernel): once
+with the continuous seed of k over nalpha classes and once under every seed given; the full-alphabet default stays the first row of
+each shape.  The classification is --classes, or the pattern a fixture of tests/golden/kmer_spec records for that nalpha.
+
 Shapes: the bench family (make_family(256, 1024, 1), protein, k = 5 / Qpamd: the defaults) and a 4096-member family of 1024
 residues (members mutated from one ancestor at rates spread over 5 .. 60 %, no indels; seeded numpy).  The counts of a sample of
 pairs are checked against the Python restatement (tests/kmerlib.py) in the same run.
-Usage: python tools/kmer_probe.py [--out profiles/NAME.json] [--shapes 256,4096]"""
+Usage: python tools/kmer_probe.py [--out profiles/NAME.json] [--shapes 256,4096] [--nalpha 14 --k 4 [--seed 1011,110101] [--classes PATTERN]]"""
 import argparse
 import json
 import os
@@ -46,13 +50,36 @@ def synthetic(many, ln, seed):
     return out
 
 
-def probe(ctx, name, seqs, reps=10):
+def recorded_pattern(nalpha):
+    import kmerspeclib as ks
+    for _, g in ks.fixtures():
+        c = ks.case(g)
+        if c["molc"] == 1 and c["nalpha"] == nalpha:
+            return c["classes"]
+    raise SystemExit("no fixture of tests/golden/kmer_spec records a protein pattern for nalpha %d: give --classes" % nalpha)
+
+
+def probe(ctx, name, seqs, reps=10, spec=None):
+    """spec: None for g2g_kmer_dist_batch with the defaults, else (nalpha, k, classes, seed) for g2g_kmer_dist_batch_spec"""
     import kmerlib
+    import kmerspeclib as ks
     from prrn_aln_amd import guide
+    if spec is None:
+        run = lambda: guide.kmer_distance(ctx, seqs, 1, want_counts=True)
+        want_counts = lambda sq, a, b: kmerlib.counts_pairs(sq, 1, 0, a, b)
+        words = lambda s: kmerlib.profile(s, 1, 5)[0]
+        k, entry = 5, "g2g_kmer_dist_batch"
+    else:
+        nalpha, k, classes, seed = spec
+        tab = ks.table(classes, 1)
+        run = lambda: guide.kmer_distance_spec(ctx, seqs, 1, k, -1, nalpha, classes, seed, want_counts=True)
+        want_counts = lambda sq, a, b: ks.counts_pairs(sq, 1, k, nalpha, classes, seed, a, b)
+        words = lambda s: ks.profile(s, tab, nalpha, k, seed)[0]
+        entry = "g2g_kmer_dist_batch_spec"
     prof, pairs, call = [], [], []
     for r in range(reps + 2):                                           # two warm-up runs: code object load, first allocation
         t0 = time.perf_counter()
-        dist, counts = guide.kmer_distance(ctx, seqs, 1, want_counts=True)
+        dist, counts = run()
         dt = (time.perf_counter() - t0) * 1e3
         if r >= 2:
             call.append(dt)
@@ -62,16 +89,16 @@ def probe(ctx, name, seqs, reps=10):
     rng = np.random.default_rng(1)
     ia, ib = rng.integers(0, n, 200), rng.integers(0, n, 200)
     keep = ia < ib
-    want = kmerlib.counts_pairs(seqs, 1, 0, ia[keep], ib[keep]) if n <= 256 else None
+    want = want_counts(seqs, ia[keep], ib[keep]) if n <= 256 else None
     if want is None:                                                    # (profiles of the sampled members only)
         ids = sorted(set(ia[keep]) | set(ib[keep]))
         at = {m: i for i, m in enumerate(ids)}
-        want = kmerlib.counts_pairs([seqs[m] for m in ids], 1, 0, [at[a] for a in ia[keep]], [at[b] for b in ib[keep]])
+        want = want_counts([seqs[m] for m in ids], [at[a] for a in ia[keep]], [at[b] for b in ib[keep]])
     got = np.array([counts[kmerlib.elem(int(a), int(b))] for a, b in zip(ia[keep], ib[keep])])
-    unq = np.array([len(np.unique(kmerlib.profile(s, 1, 5)[0])) for s in seqs[:64]])
+    unq = np.array([len(words(s)) for s in seqs[:64]])
     med = statistics.median
     return {"shape": name, "members": n, "residues": int(np.median([len(s) for s in seqs])), "pairs": n * (n - 1) // 2,
-            "k": 5, "measure": "Qpamd", "distinct_words_median_of_64": int(np.median(unq)),
+            "entry": entry, "k": k or 5, "nalpha": spec[0] if spec else 20, "seed": (spec[3] if spec else None), "measure": "Qpamd", "distinct_words_median_of_64": int(np.median(unq)),
             "profile_ms": round(med(prof), 4), "profile_ms_min_max": [round(min(prof), 4), round(max(prof), 4)],
             "pairs_ms": round(med(pairs), 4), "pairs_ms_min_max": [round(min(pairs), 4), round(max(pairs), 4)],
             "call_ms": round(med(call), 3), "call_ms_min_max": [round(min(call), 3), round(max(call), 3)], "runs": reps,
@@ -95,20 +122,31 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--shapes", default="256,4096")
+    ap.add_argument("--nalpha", type=int, default=0)
+    ap.add_argument("--k", type=int, default=0)
+    ap.add_argument("--seed", default="", help="comma-separated seed strings")
+    ap.add_argument("--classes", default="", help="classification pattern; default: the one a kmer_spec fixture records for --nalpha")
     a = ap.parse_args()
+    specs = []
+    if a.nalpha or a.k or a.seed:
+        nalpha = a.nalpha or 20
+        classes = a.classes or (recorded_pattern(nalpha) if nalpha != 20 else None)
+        specs = [(nalpha, a.k, classes, None)] + [(nalpha, a.k, classes, sd) for sd in a.seed.split(",") if sd]
     from prrn_aln_amd import engine
     ctx = engine.Context()
     ctx.set_option("KMER_TIMING", 1)
     rows = []
     for s in a.shapes.split(","):
         if s == "256":
-            seqs = bench_family()
-            r = probe(ctx, "bench family make_family(256, 1024, 1)", seqs)
-            r["alnscored_distance_matrix_ms"] = alnscored(ctx, seqs)
+            seqs, name = bench_family(), "bench family make_family(256, 1024, 1)"
         else:
-            r = probe(ctx, "synthetic %s x 1024" % s, synthetic(int(s), 1024, int(s)))
-        print(json.dumps(r), flush=True)
-        rows.append(r)
+            seqs, name = synthetic(int(s), 1024, int(s)), "synthetic %s x 1024" % s
+        for spec in [None] + specs:
+            r = probe(ctx, name, seqs, spec=spec)
+            if s == "256" and spec is None:
+                r["alnscored_distance_matrix_ms"] = alnscored(ctx, seqs)
+            print(json.dumps(r), flush=True)
+            rows.append(r)
     ctx.close()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
