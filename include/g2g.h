@@ -521,6 +521,41 @@ int        g2g_kmer_dist_batch_spec(g2g_ctx *ctx, const g2g_kmer_spec *sp, int n
 /* host only, no context; classes and nclasses are not looked at */
 int        g2g_kmer_dist_from_counts_spec(const g2g_kmer_spec *sp, int npairs, const int32_t *counts, double *dist);
 
+/* ---- the conserved regions of an MSA ---------------------------------------------------------------------------------
+ * <-> Ssrel::consreg / Ssrel::constwo (reference src/consreg.cc:438-518), the first step of prrn's default refinement
+ * (IterMsa::preprrn, src/prrn5.cc:785-839): the MSA is cut at every branch of its weighting tree into two sons that keep the
+ * father's columns; per division a PwdM and one walk over the columns -- s = sim2 of the column plus the gap term of a diagonal
+ * step, cons2_ng / _nv / _hf / _pf (consreg.cc:170-406) by the PwdM's banded mode -- and a thresholded running sum over s gives
+ * ranges of columns; the ranges of all divisions are intersected (cmnrng, src/css.cc:261-282).  The column scores and the scan
+ * run on the GPU (csrc/g2g_consreg.hip: one workgroup per division), in the reference's order of double additions.
+ * Not on this path: consregss / mayfuse (group fusing), Conserved1, findoutliers, refinement restricted to ranges.
+ * (Entry points added without a change of g2g_abi_version.) */
+typedef struct { int32_t left, right; } g2g_range;
+
+/* <-> Ssrel::constwo on n built pairs whose two groups have the SAME length (juxtaposed sons of one MSA).
+   thr: ALPRM::thr.  ranges[i] malloc'ed (g2g_free), nranges[i] entries, ascending, columns of the groups.
+   colscore may be NULL; else colscore[i] receives len_i doubles, the s of every column (malloc'ed).
+   status (n ints) may be NULL.  G2G_ERR_MODE: a pair in a mode that is not banded, annotated groups, groups with discounted
+   terminal gaps; G2G_ERR_ARG: groups of unequal length or not standing whole (left = 0, right = len), thr <= 0.  A pair that
+   cannot be served fails the call, g2g_last_error names it.  Arguments are checked before the device is asked for.           */
+int g2g_constwo_batch(g2g_ctx *ctx, int n, g2g_pwdm *const *pw, double thr,
+                      g2g_range **ranges, int *nranges, double **colscore, int *status);
+
+/* <-> Ssrel::consreg(msd, dissim): all 2 many - 3 branches of `tree`, sons extracted with every column kept,
+   weight (many doubles, may be NULL) handed down as Seq::extseq does; the intersection of the divisions'
+   ranges, or with dissim its complement in [0, len).  prm is the caller's localprm (u, v, scale, ls, k1,
+   tgapf, simmtx = the matrix the reference would use: number 1); prm->banded must be 1.
+   The reference's localprm (consreg.cc:39-40): u 3, v 10, u0 0, u1 0, tgapf 1, scale 1, k1 7, ls 2, sh 100, thr 35.
+   *out malloc'ed (g2g_free; an empty result is a valid pointer with *nout = 0).
+   G2G_ERR_MODE: banded != 1, u0 > 0, tgapf != 1; G2G_ERR_ARG: many < 3, thr <= 0, a malformed tree.                          */
+int g2g_consreg(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                const double *weight, const g2g_tree *tree, int dissim, g2g_range **out, int *nout);
+
+/* host only, no context: what g2g_consreg finishes with, on plain ascending lists of disjoint ranges.  dissim = 0: cmnrng(a, b, 0),
+   the intersection with empty pieces dropped (len is not read); dissim = 1: complerng, [0, len) without the ranges of a (b is not
+   read).  *out malloc'ed (g2g_free). */
+int g2g_ranges_combine(const g2g_range *a, int na, const g2g_range *b, int nb, int dissim, int len, g2g_range **out, int *nout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,11 @@ class KTreeOut(C.Structure):
                 ("res", c_f64p), ("vol", c_f64p), ("cur", c_f64p)]
 
 
+class Range(C.Structure):
+    """g2g_range: columns [left, right) of an MSA (the reference's RANGE)"""
+    _fields_ = [("left", C.c_int32), ("right", C.c_int32)]
+
+
 class KmerParams(C.Structure):
     """g2g_kmer_params: molecule, word length and DistMes of g2g_kmer_dist_batch (0 / -1: the reference's defaults)"""
     _fields_ = [("molc", C.c_int32), ("k", C.c_int32), ("measure", C.c_int32), ("reserved", C.c_int32)]

@@ -91,6 +91,12 @@ def lib():
     L.g2g_kmer_dist_batch_spec.argtypes = [C.c_void_p, C.POINTER(_abi.KmerSpec), C.c_int, C.POINTER(_abi.DSeq), C.c_int,
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), _abi.c_f64p, C.POINTER(C.c_int32)]
     L.g2g_kmer_dist_from_counts_spec.argtypes = [C.POINTER(_abi.KmerSpec), C.c_int, C.POINTER(C.c_int32), _abi.c_f64p]
+    RP = C.POINTER(_abi.Range)
+    L.g2g_constwo_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.POINTER(RP), C.POINTER(C.c_int),
+                                    C.POINTER(_abi.c_f64p), C.POINTER(C.c_int)]
+    L.g2g_consreg.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_double, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
+                              C.c_int, C.POINTER(RP), C.POINTER(C.c_int)]
+    L.g2g_ranges_combine.argtypes = [RP, C.c_int, RP, C.c_int, C.c_int, C.c_int, C.POINTER(RP), C.POINTER(C.c_int)]
     bind_level1(L)
     _lib = L
     return L

@@ -1,0 +1,466 @@
+// g2g_consreg.hip -- the conserved regions of an MSA: Ssrel::consreg / Ssrel::constwo (reference src/consreg.cc:438-518).
+// The reference cuts the MSA at every branch of its weighting tree into two sons that keep the father's columns, builds a PwdM
+// for the pair and walks the columns once: per column a group-to-group similarity plus the gap term of a diagonal step
+// (cons2_ng / _nv / _hf / _pf, consreg.cc:170-406), a thresholded running sum over the column scores gives ranges, and the
+// ranges of all divisions are intersected (cmnrng, src/css.cc:261-282).
+//   g2g_consreg_kernel: one workgroup per division, lanes across the columns of a tile of CR_T columns.
+//     1. members whose gap run in front of the column is read (_hf: b's, _nv: both sides'): one ballot per member and wave says
+//        which of the tile's columns hold a residue; the run length of (member, column) is the distance to the nearest set bit
+//        below the column -- in the lane's own wave, the waves in front of it, or the column carried in from earlier tiles
+//        (Seq::pregap with left = 0 followed by incrgap, src/seq.cc:1870-1883, src/mgaps.cc:431-440).
+//     2. a lane forms s of its column with the scorers of g2g_kernels.hip (sim2, crg2, newgap4) and stores it to LDS.
+//     3. lane 0 runs the reference's recurrence over the tile's scores in column order; its scalars stay in registers from tile
+//        to tile.  Ranges go to the division's slot in HBM.
+// Plain launch on the context's stream; no atomics, no waits on other workgroups.
+#include <hip/hip_runtime.h>
+
+#define CR_T 256                      /* columns per tile = threads per workgroup */
+#define CR_W (CR_T / 64)              /* waves */
+#define CR_NV_MEM 8                   /* members of an _nv division (2 nj + ni < thr_gfq_21 = 8 allows four) */
+
+struct ConsregArgs {
+    double vthr;                      // PwdM::Vthr = Vab * thr (src/maln2.cc:235)
+    int2 *ranges; int cap;            // the division's slot
+    int *nranges;                     // ranges found (may exceed cap: the host reports it)
+    double *colscore;                 // len doubles, or NULL
+};
+
+// run length of member j in front of column c (absolute), from the tile's residue masks and the carried column
+__device__ __forceinline__ int cr_runlen(const unsigned long long *mask, const int *last, const int j, const int c0, const int c, const int wave, const int lane)
+{
+    unsigned long long m = mask[j * CR_W + wave] & ((1ull << lane) - 1ull);
+    int w = wave;
+    while (!m && w > 0) { --w; m = mask[j * CR_W + w]; }
+    const int lastp1 = m ? c0 + w * 64 + (63 - __clzll((long long) m)) + 1 : last[j];
+    return c - lastp1;
+}
+
+// PwdM::newgap2(asi, bs, glb), src/maln2.cc:850-879 (the _hf form of consreg only: the DP's newgap2 has dynamic lists)
+__device__ double cr_newgap2(const DevProb &P, const int c, const unsigned long long *mask, const int *last, const int c0, const int wave, const int lane)
+{
+    double g = 0;
+    const uint8_t *bs = res_at(P.b, c);
+    const double *wt = P.b.weight;
+    const SList adf = gfq_at(P.a, 1, c), acf = gfq_at(P.a, 0, c);
+    for (int j = 0; j < P.b.many; ++j) {
+        const double w = wt ? wt[j] : 1;
+        const int glb = cr_runlen(mask, last, j, c0, c, wave, lane);
+        if (bs[j] > 1) {
+            for (int k = 0; adf.glen[k] >= 0; ++k) {
+                if (glb < adf.glen[k]) break;
+                g += adf.freq[k] * w;
+            }
+        } else {
+            const double bu = 1;                               // mSeq::gapdensity of a gap without terminal discount (mseq.h:148-153)
+            for (int k = 0; acf.glen[k] >= 0; ++k) {
+                if (acf.glen[k] >= glb) g += acf.freq[k] * w * bu;
+                else break;
+            }
+        }
+    }
+    return P.weighted_gop * g;
+}
+
+extern "C" __global__ void __launch_bounds__(CR_T) g2g_consreg_kernel(const DevProb *probs, const ConsregArgs *args)
+{
+    extern __shared__ __align__(16) unsigned char cr_dyn[];
+    __shared__ double sc[CR_T];
+    __shared__ int gl[CR_NV_MEM * CR_T];
+    __shared__ int2 zero_delta[2];                             // ZeroDelta: newgap4 over it is newgap(cf, df), src/gfreq.cc:493-505
+    __shared__ DevProb P;
+    const ConsregArgs A = args[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < (int) (sizeof(DevProb) / 4); i += CR_T) ((int *) &P)[i] = ((const int *) &probs[blockIdx.x])[i];
+    __syncthreads();
+    const int len = P.a.right, kind = P.kind;
+    const int an = P.a.many, bn = P.b.many;
+    const int nm = kind == 3 ? an + bn : kind == 1 ? bn : 0;   // members whose gap runs are read
+    unsigned long long *mask = (unsigned long long *) cr_dyn;  // [nm][CR_W]
+    int *last = (int *) (mask + (size_t) nm * CR_W);           // [nm]: column behind the member's last residue in front of the tile
+    for (int j = tid; j < nm; j += CR_T) last[j] = 0;
+    if (tid == 0) { zero_delta[0] = make_int2(0, 0); zero_delta[1] = make_int2(INT_MAX, 0); }
+    DList zd; zd.p = zero_delta; zd.s = 1;
+    // the scan's scalars (consreg.cc:172-182; `sum` is only printed there)
+    double scr = 0, mxv = 0;
+    int rl = 0, rr = 0, nr = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < len; c0 += CR_T) {
+        const int c = c0 + tid;
+        const bool live = c < len;
+        const int cc = live ? c : len - 1;
+        for (int j = 0; j < nm; ++j) {
+            const bool ina = kind == 3 && j < an;
+            const uint8_t r = ina ? res_at(P.a, cc)[j] : res_at(P.b, cc)[kind == 3 ? j - an : j];
+            const unsigned long long m = __ballot(live && r > 1);
+            if (lane == 0) mask[j * CR_W + wave] = m;
+        }
+        __syncthreads();
+        if (live) {
+            double s = sim2(P, c, c);
+            if (kind == 3) {
+                for (int j = 0; j < nm; ++j) gl[j * CR_T + tid] = cr_runlen(mask, last, j, c0, c, wave, lane);
+                s = s + crg2(P, gl + tid, gl + an * CR_T + tid, CR_T, c, c, 0);
+            } else if (kind == 1) {
+                s = s + cr_newgap2(P, c, mask, last, c0, wave, lane);
+            } else if (kind == 2) {
+                s = s + newgap4(gfq_at(P.a, 0, c), zd, gfq_at(P.b, 1, c), zd) * P.basic_gop
+                      + newgap4(gfq_at(P.b, 0, c), zd, gfq_at(P.a, 1, c), zd) * P.basic_gop;
+            }
+            sc[tid] = s;
+            if (A.colscore) A.colscore[c] = s;
+        }
+        __syncthreads();
+        for (int j = tid; j < nm; j += CR_T)
+            for (int w = CR_W - 1; w >= 0; --w) {
+                const unsigned long long m = mask[j * CR_W + w];
+                if (m) { last[j] = c0 + w * 64 + (63 - __clzll((long long) m)) + 1; break; }
+            }
+        if (tid == 0) {
+            const int n = len - c0 < CR_T ? len - c0 : CR_T;
+            for (int k = 0; k < n; ++k) {
+                const double s = sc[k];
+                const int i = c0 + k;
+                if (scr == 0 && s > 0) rl = i;
+                scr += s;
+                if (scr < 0) scr = 0;
+                else if (scr >= A.vthr && scr > mxv) { mxv = scr; rr = i + 1; }
+                if (mxv > 0 && (scr <= 0 || scr < mxv - A.vthr)) {
+                    if (nr < A.cap) A.ranges[nr] = make_int2(rl, rr);
+                    ++nr;
+                    mxv = scr = 0;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (scr >= A.vthr) { if (nr < A.cap) A.ranges[nr] = make_int2(rl, rr); ++nr; }
+        *A.nranges = nr;
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+namespace {
+typedef std::vector<g2g_range> CrRanges;
+// cmnrng(a, b, 0), src/css.cc:261-282: the intersection of two ascending lists of disjoint ranges, empty pieces dropped
+CrRanges cr_cmnrng(const CrRanges &a, const CrRanges &b)
+{
+    CrRanges out;
+    size_t i = 0, j = 0;
+    while (i < a.size() && j < b.size()) {
+        const bool a_low = a[i].right <= b[j].right;              // ll: the range that ends first
+        const g2g_range &ll = a_low ? a[i] : b[j], &uu = a_low ? b[j] : a[i];
+        if (ll.right >= uu.left) {
+            g2g_range c;
+            c.left = std::max(a[i].left, b[j].left);
+            c.right = ll.right;
+            if (c.right - c.left > 0) out.push_back(c);
+        }
+        if (a_low) ++i; else ++j;
+    }
+    return out;
+}
+// complerng(c, a), src/css.cc:313-336, with c the single range [left, right)
+CrRanges cr_complerng(int left, int right, const CrRanges &r)
+{
+    CrRanges out;
+    g2g_range b;
+    b.left = left;
+    for (const g2g_range &x : r) {
+        b.right = x.left;
+        if (b.left < b.right) out.push_back(b);
+        b.left = x.right;
+    }
+    b.right = right;
+    if (b.left < b.right) out.push_back(b);
+    return out;
+}
+g2g_range *cr_hand_out(const CrRanges &r)
+{
+    g2g_range *p = (g2g_range *) malloc(sizeof(g2g_range) * (r.size() ? r.size() : 1));
+    if (p && !r.empty()) memcpy(p, r.data(), sizeof(g2g_range) * r.size());
+    return p;
+}
+void cr_note_ms(g2g_ctx *ctx, const char *name, double ms, bool add)
+{
+    if (add) { const char *old = g2g_opt(ctx, name); if (old) ms += atof(old); }
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.6f", ms);
+    ctx->opt[name] = std::make_pair(true, std::string(buf));
+}
+double cr_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+}
+
+// host only, no context: cmnrng (dissim = 0: the intersection of a and b) or complerng (dissim = 1: [0, len) without a; b is not
+// read) on plain lists -- what g2g_consreg finishes with
+extern "C" int g2g_ranges_combine(const g2g_range *a, int na, const g2g_range *b, int nb, int dissim, int len, g2g_range **out, int *nout)
+{
+    if (!out || !nout || na < 0 || nb < 0 || (na && !a) || (!dissim && nb && !b) || (dissim && len < 0)) return G2G_ERR_ARG;
+    const CrRanges ra(a, a + na);
+    CrRanges r;
+    if (dissim) r = cr_complerng(0, len, ra);
+    else r = cr_cmnrng(ra, CrRanges(b, b + nb));
+    *out = cr_hand_out(r);
+    *nout = (int) r.size();
+    return *out ? G2G_OK : G2G_ERR_NOMEM;
+}
+
+extern "C" int g2g_constwo_batch(g2g_ctx *ctx, int n, g2g_pwdm *const *pw, double thr, g2g_range **ranges, int *nranges, double **colscore, int *status)
+{
+    const char *who = "g2g_constwo_batch";
+    if (n < 0 || (n && (!pw || !ranges || !nranges))) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if (!(thr > 0)) { g2g_set_error("%s: thr must be positive", who); return G2G_ERR_ARG; }
+    for (int i = 0; i < n; ++i) { ranges[i] = 0; nranges[i] = 0; if (colscore) colscore[i] = 0; if (status) status[i] = G2G_OK; }
+    std::vector<const g2g_problem *> prob((size_t) n);
+    std::vector<double> vthr((size_t) n);
+    size_t nm_max = 0, cols = 0;
+    for (int i = 0; i < n; ++i) {
+        const g2g_problem *p = pw[i] ? g2g_pwdm_problem(pw[i]) : 0;
+        g2g_spparams sp;
+        if (!p || g2g_pwdm_spparams(pw[i], &sp) != G2G_OK) { g2g_set_error("%s: a NULL pair", who); return G2G_ERR_ARG; }
+        int rc = G2G_OK;
+        char msg[160] = "";
+        if (p->alnmode < G2G_NGP_ALB || p->alnmode > G2G_NTV_ALB) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: mode %d is not a banded mode (constwo's switch reads the banded names only)", i, p->alnmode); }
+        else if (p->a.npfq > 0 || p->b.npfq > 0) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: annotated (spliced) groups are not on this path", i); }
+        else if (p->a.nils || p->b.nils) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: groups with discounted terminal gaps are not on this path", i); }
+        else if (p->a.len != p->b.len || p->a.left != 0 || p->b.left != 0 || p->a.right != p->a.len || p->b.right != p->b.len) { rc = G2G_ERR_ARG; snprintf(msg, sizeof msg, "pair %d: the two groups must have the same length and stand whole (%d and %d columns)", i, p->a.len, p->b.len); }
+        else if (p->alnmode == G2G_NTV_ALB && p->a.many + p->b.many > CR_NV_MEM) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: a naive-record division of %d members", i, p->a.many + p->b.many); }
+        if (rc == G2G_OK && (rc = check_problem(p)) != G2G_OK) snprintf(msg, sizeof msg, "pair %d: not a problem of this library (status %d)", i, rc);
+        if (rc != G2G_OK) { if (status) status[i] = rc; g2g_set_error("g2g_constwo_batch: %s", msg); return rc; }
+        prob[(size_t) i] = p;
+        vthr[(size_t) i] = sp.vab * thr;
+        const int kind = kind_of(p->alnmode);
+        const size_t nm = kind == 3 ? (size_t) p->a.many + p->b.many : kind == 1 ? (size_t) p->b.many : 0;
+        nm_max = std::max(nm_max, nm);
+        cols += (size_t) p->a.len;
+    }
+    const size_t lds = (nm_max * (8 * CR_W + 4) + 15) & ~(size_t) 15;
+    if (lds > 48 * 1024) { g2g_set_error("%s: a gap-free group of more than 1365 members on the _hf path", who); return G2G_ERR_MODE; }
+    if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
+    if (!ctx->ok) return G2G_ERR_NODEVICE;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (n == 0) return G2G_OK;
+    // the inputs as g2g_batch_prepare packs them (arrays a device builder left in HBM are read where they lie), and nothing else:
+    // no DP state, no trace
+    std::vector<DevProb> dp((size_t) n);
+    std::vector<ConsregArgs> ar((size_t) n);
+    std::vector<DevPatch> patches;
+    std::vector<size_t> o_rng((size_t) n), o_col((size_t) n);
+    size_t in_bytes = 0, total = 0;
+    char *dev = 0;
+    size_t dev_cap = 0;
+    hipError_t e = hipSuccess;
+    std::vector<int> hn((size_t) n, 0);
+    size_t o_nr = 0, o_probs = 0, o_args = 0;
+    {
+        Blob bl(ctx);
+        bl.grow(staging_estimate(ctx, n, prob.data()) + sizeof(ConsregArgs) * (size_t) n);
+        o_probs = bl.put(0, 0);
+        bl.extend(o_probs + sizeof(DevProb) * (size_t) n);
+        o_args = bl.put(0, 0);
+        bl.extend(o_args + sizeof(ConsregArgs) * (size_t) n);
+        for (int i = 0; i < n; ++i) pack_problem(bl, prob[(size_t) i], dp[(size_t) i], patches);
+        bl.flush();
+        if (bl.oom) { g2g_set_error("%s: host staging buffer: out of (pinned) memory", who); return G2G_ERR_NOMEM; }
+        in_bytes = (bl.size() + 255) & ~(size_t) 255;
+        total = in_bytes;
+        o_nr = total; total += (4 * (size_t) n + 255) & ~(size_t) 255;
+        for (int i = 0; i < n; ++i) {
+            const size_t len = (size_t) prob[(size_t) i]->a.len, cap = len / 2 + 2;
+            o_rng[(size_t) i] = total; total += (sizeof(int2) * cap + 15) & ~(size_t) 15;
+            o_col[(size_t) i] = total; if (colscore) total += (8 * len + 15) & ~(size_t) 15;
+        }
+        dev = (char *) pool_take(ctx, total, &dev_cap);
+        if (!dev) { g2g_set_error("%s: out of device memory", who); (void) hipGetLastError(); return G2G_ERR_NOMEM; }
+        for (int i = 0; i < n; ++i) {
+            rebase_problem(dp[(size_t) i], dev);
+            ConsregArgs &a = ar[(size_t) i];
+            a.vthr = vthr[(size_t) i];
+            a.ranges = (int2 *) (dev + o_rng[(size_t) i]); a.cap = prob[(size_t) i]->a.len / 2 + 2;
+            a.nranges = (int *) (dev + o_nr) + i;
+            a.colscore = colscore ? (double *) (dev + o_col[(size_t) i]) : 0;
+        }
+        for (const DevPatch &pt : patches) *pt.field = pt.value;
+        memcpy(bl.data() + o_probs, dp.data(), sizeof(DevProb) * (size_t) n);
+        memcpy(bl.data() + o_args, ar.data(), sizeof(ConsregArgs) * (size_t) n);
+        e = hipMemcpyAsync(dev, bl.data(), bl.size(), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);        // (the staging buffer goes back to the context with bl)
+    }
+    const bool timed = g2g_opt(ctx, "CONSREG_TIMING") != 0;                // diagnostic switch: device events around the kernel (tools/consreg_probe.py)
+    if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[0], ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(g2g_consreg_kernel, dim3((unsigned) n), dim3(CR_T), lds, ctx->stream, (const DevProb *) (dev + o_probs), (const ConsregArgs *) (dev + o_args));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[1], ctx->stream);
+    // everything behind the inputs comes back in one copy
+    std::vector<char> back(total - in_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    else (void) hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && timed) {                                        // read back as option CONSREG_KERNEL_MS (summed over the calls since it was cleared)
+        float ms = 0;
+        e = hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+        cr_note_ms(ctx, "CONSREG_KERNEL_MS", ms, true);
+    }
+    pool_give(ctx, dev, dev_cap);
+    if (e != hipSuccess) { g2g_set_error("g2g_constwo_batch: %s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
+    int rc = G2G_OK;
+    for (int i = 0; i < n && rc == G2G_OK; ++i) {
+        const int len = prob[(size_t) i]->a.len, cap = len / 2 + 2;
+        const int nr = ((const int *) (back.data() + (o_nr - in_bytes)))[i];
+        if (nr < 0 || nr > cap) { g2g_set_error("%s: a division produced more ranges than its slot holds", who); rc = G2G_ERR_DEVICE; break; }
+        ranges[i] = (g2g_range *) malloc(sizeof(g2g_range) * (size_t) (nr ? nr : 1));
+        if (!ranges[i]) { rc = G2G_ERR_NOMEM; break; }
+        memcpy(ranges[i], back.data() + (o_rng[(size_t) i] - in_bytes), sizeof(g2g_range) * (size_t) nr);
+        nranges[i] = nr;
+        if (colscore) {
+            colscore[i] = (double *) malloc(8 * (size_t) len);
+            if (!colscore[i]) { rc = G2G_ERR_NOMEM; break; }
+            memcpy(colscore[i], back.data() + (o_col[(size_t) i] - in_bytes), 8 * (size_t) len);
+        }
+    }
+    if (rc != G2G_OK)
+        for (int i = 0; i < n; ++i) { free(ranges[i]); ranges[i] = 0; nranges[i] = 0; if (colscore) { free(colscore[i]); colscore[i] = 0; } }
+    return rc;
+}
+
+extern "C" int g2g_consreg(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,
+                           const g2g_tree *tree, int dissim, g2g_range **out, int *nout)
+{
+    const char *who = "g2g_consreg";
+    if (!prm || !codes || !tree || !out || !nout || len < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if (many < 3) { g2g_set_error("%s: fewer than three members have no division into two sons", who); return G2G_ERR_ARG; }
+    if (!(thr > 0)) { g2g_set_error("%s: thr must be positive", who); return G2G_ERR_ARG; }
+    if (tree->n_nodes != 2 * many - 1 || !tree->left || !tree->right || !tree->parent) { g2g_set_error("%s: the tree must have 2 * many - 1 nodes", who); return G2G_ERR_ARG; }
+    if (prm->banded != 1) { g2g_set_error("%s: banded must be 1 (with algmode.bnd = 0 every mode falls into constwo's default branch)", who); return G2G_ERR_MODE; }
+    if (prm->u0 > 0) { g2g_set_error("%s: ether scorers (u0 > 0) are not on this path", who); return G2G_ERR_MODE; }
+    // (mkthick reads tgapf from the global alprm, src/mseq.cc:165-166: prm->tgapf stands for it here)
+    if ((float) prm->tgapf != 1.f) { g2g_set_error("%s: the terminal-gap discount is not on this path", who); return G2G_ERR_MODE; }
+    *out = 0; *nout = 0;
+    // the branches: node r = 0 .. 2 many - 4 (Randiv::tree_tab, src/randiv.cc:120-156; the root's second child repeats its first);
+    // bin2lst2g (:88-100) puts the members below the node into son 1 and the others into son 0, both ascending
+    const int nn = tree->n_nodes, cycle = 2 * many - 3;
+    int root = -1;
+    for (int k = 0; k < nn; ++k) {
+        const int l = tree->left[k], r = tree->right[k], p = tree->parent[k];
+        if (l < -1 || l >= nn || r < -1 || r >= nn || p < -1 || p >= nn || (k < many ? (l != -1 || r != -1) : (l < 0 || r < 0 || l == r))) { g2g_set_error("%s: malformed tree", who); return G2G_ERR_ARG; }
+        if (p < 0) { if (root >= 0) { g2g_set_error("%s: malformed tree (two roots)", who); return G2G_ERR_ARG; } root = k; }
+    }
+    if (root < many) { g2g_set_error("%s: malformed tree (no root)", who); return G2G_ERR_ARG; }
+    std::vector<std::vector<int>> inside((size_t) nn);
+    {   // leaves below every node, children before parents (an explicit post-order walk; a node met twice is a malformed tree)
+        std::vector<char> seen((size_t) nn, 0);
+        std::vector<std::pair<int, int>> st(1, std::make_pair(root, 0));
+        int cnt = 0;
+        while (!st.empty()) {
+            const int k = st.back().first;
+            if (st.back().second == 0) {
+                if (seen[(size_t) k]) { g2g_set_error("%s: malformed tree (a node is reachable twice)", who); return G2G_ERR_ARG; }
+                seen[(size_t) k] = 1; ++cnt;
+                st.back().second = 1;
+                if (tree->left[k] >= 0) { st.push_back(std::make_pair(tree->right[k], 0)); st.push_back(std::make_pair(tree->left[k], 0)); }
+                else inside[(size_t) k].push_back(k);
+            } else {
+                if (tree->left[k] >= 0) {
+                    std::vector<int> &v = inside[(size_t) k];
+                    v = inside[(size_t) tree->left[k]];
+                    v.insert(v.end(), inside[(size_t) tree->right[k]].begin(), inside[(size_t) tree->right[k]].end());
+                    std::sort(v.begin(), v.end());
+                }
+                st.pop_back();
+            }
+        }
+        if (cnt != nn) { g2g_set_error("%s: malformed tree (not every node hangs below the root)", who); return G2G_ERR_ARG; }
+    }
+    std::vector<int> branches;
+    for (int k = 0; k < nn; ++k) {
+        if (k == root) continue;
+        // the two children of the root cut the same branch: the later one is dropped (with the reference's numbering that is node 2 many - 3)
+        if (tree->parent[k] == root && k == std::max(tree->left[root], tree->right[root])) continue;
+        branches.push_back(k);
+    }
+    if ((int) branches.size() != cycle) { g2g_set_error("%s: malformed tree (parent links)", who); return G2G_ERR_ARG; }
+    if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
+    if (!ctx->ok) return G2G_ERR_NODEVICE;
+    const bool timed = g2g_opt(ctx, "CONSREG_TIMING") != 0;
+    if (timed) { ctx->opt.erase("CONSREG_KERNEL_MS"); }
+    double t_build = 0, t_two = 0, t_host = 0;
+    // chunks: the host arrays of a chunk's groups and their device twins stay within about 128 M residue codes
+    size_t chunk = ((size_t) 128 << 20) / ((size_t) many * (size_t) len);
+    chunk = std::max<size_t>(1, std::min<size_t>(chunk, 512));
+    // the first chunk is small: where nothing is conserved across all branches the intersection is empty after a few divisions and
+    // the reference stops there (consreg.cc:506) -- the result does not depend on where the loop stops
+    size_t first = std::min<size_t>(chunk, 8);
+    if (const char *o = g2g_opt(ctx, "CONSREG_CHUNK")) { const int v = atoi(o); if (v >= 1) first = chunk = (size_t) v; }
+    const bool all_divisions = g2g_opt(ctx, "CONSREG_NO_EARLY_STOP") != 0;     // diagnostic switch (tools/consreg_probe.py): every division is scored
+    if (all_divisions) first = chunk;
+    CrRanges united(1);
+    united[0].left = 0; united[0].right = len;
+    int rc = G2G_OK;
+    for (size_t b0 = 0, step = first; b0 < branches.size() && rc == G2G_OK; b0 += step, step = chunk) {
+        const int nb = (int) std::min(step, branches.size() - b0);
+        std::vector<g2g_group *> ga((size_t) nb, (g2g_group *) 0), gb((size_t) nb, (g2g_group *) 0);
+        std::vector<g2g_pwdm *> pw((size_t) nb, (g2g_pwdm *) 0);
+        const double t0 = cr_now();
+        {   // Ssrel::dividseq: extseq(sons[s], lstbuf[s], CPY_SEQ + CPY_NBR) -- every column kept; weights handed down / nfact = 1, a
+            // single member gets 1 (Seq::extseq, src/seq.cc:1096-1153)
+            std::atomic<int> next(0);
+            std::atomic<int> bad(0);
+            auto work = [&]() {
+                std::vector<uint8_t> c;
+                std::vector<double> w;
+                std::vector<char> in((size_t) many);
+                for (int k; (k = next.fetch_add(1)) < nb; ) {
+                    const std::vector<int> &ins = inside[(size_t) branches[b0 + (size_t) k]];
+                    std::fill(in.begin(), in.end(), 0);
+                    for (int l : ins) in[(size_t) l] = 1;
+                    std::vector<int> outs;
+                    for (int i = 0; i < many; ++i) if (!in[(size_t) i]) outs.push_back(i);
+                    const std::vector<int> *lst[2] = {&outs, &ins};
+                    g2g_group *made[2] = {0, 0};
+                    for (int s = 0; s < 2; ++s) {
+                        const int m = (int) lst[s]->size();
+                        c.resize((size_t) len * m);
+                        for (int r = 0; r < len; ++r) for (int i = 0; i < m; ++i) c[(size_t) r * m + i] = codes[(size_t) r * many + (*lst[s])[(size_t) i]];
+                        w.clear();
+                        if (weight) for (int i = 0; i < m; ++i) w.push_back(m == 1 ? 1. : weight[(*lst[s])[(size_t) i]]);
+                        made[s] = g2g_group_create(ctx, prm, m, len, c.data(), weight ? w.data() : 0);
+                    }
+                    ga[(size_t) k] = made[0]; gb[(size_t) k] = made[1];
+                    if (!made[0] || !made[1]) bad.store(1);
+                }
+            };
+            unsigned nthr = std::thread::hardware_concurrency();
+            if (nthr > 16) nthr = 16;
+            if (nthr < 1) nthr = 1;
+            std::vector<std::thread> th;
+            for (unsigned t = 1; t < nthr && (int) t < nb; ++t) { try { th.emplace_back(work); } catch (...) { break; } }
+            work();
+            for (auto &t : th) t.join();
+            if (bad.load()) { g2g_set_error("%s: building a son failed", who); rc = G2G_ERR_ARG; }
+        }
+        if (rc == G2G_OK) rc = g2g_pwdm_create_batch(ctx, prm, nb, ga.data(), gb.data(), 0, pw.data());
+        const double t1 = cr_now();
+        t_build += t1 - t0;
+        std::vector<g2g_range *> rg((size_t) nb, (g2g_range *) 0);
+        std::vector<int> nr((size_t) nb, 0);
+        if (rc == G2G_OK) rc = g2g_constwo_batch(ctx, nb, pw.data(), thr, rg.data(), nr.data(), 0, 0);
+        const double t2 = cr_now();
+        t_two += t2 - t1;
+        for (int k = 0; k < nb && rc == G2G_OK; ++k) {            // united = cmnrng(prv, rng, 0); the order does not matter
+            united = cr_cmnrng(united, CrRanges(rg[(size_t) k], rg[(size_t) k] + nr[(size_t) k]));
+        }
+        t_host += cr_now() - t2;
+        for (int k = 0; k < nb; ++k) { free(rg[(size_t) k]); if (pw[(size_t) k]) g2g_pwdm_free(pw[(size_t) k]); if (ga[(size_t) k]) g2g_group_free(ga[(size_t) k]); if (gb[(size_t) k]) g2g_group_free(gb[(size_t) k]); }
+        if (united.empty() && !all_divisions) break;                // (consreg.cc:506)
+    }
+    if (rc != G2G_OK) return rc;
+    const double t3 = cr_now();
+    if (dissim) united = cr_complerng(0, len, united);
+    *out = cr_hand_out(united);
+    *nout = (int) united.size();
+    t_host += cr_now() - t3;
+    if (timed) { cr_note_ms(ctx, "CONSREG_BUILD_MS", t_build, false); cr_note_ms(ctx, "CONSREG_CONSTWO_MS", t_two, false); cr_note_ms(ctx, "CONSREG_HOST_MS", t_host, false); }
+    return *out ? G2G_OK : G2G_ERR_NOMEM;
+}

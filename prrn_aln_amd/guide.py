@@ -231,3 +231,101 @@ def distance_matrix(ctx, prm: "_abi.Params", seqs: Sequence[np.ndarray], simmtx:
         raise G2GError("alnScoreD failed for %d pairs (first status %d)" % (int((st != 0).sum()), int(st[st != 0][0])))
     selfs = np.array([self_score(s, simmtx) for s in seqs])
     return 100.0 * scores_to_dist(scores, ia, ib, [len(s) for s in seqs], selfs, prm.u)
+
+
+# ---- the conserved regions of an MSA (the step in front of prrn's default refinement) ----------------------------------------------
+def _take_ranges(ptr, n) -> np.ndarray:
+    out = np.zeros((n, 2), np.int32)
+    if n and ptr:
+        out[:] = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), shape=(2 * n,)).reshape(-1, 2)
+    if ptr:
+        lib().g2g_free(ptr)
+    return out
+
+
+def _range_array(r):
+    r = np.ascontiguousarray(r, np.int32).reshape(-1, 2)
+    buf = (_abi.Range * max(1, len(r)))()
+    if len(r):
+        C.memmove(buf, r.ctypes.data, r.nbytes)
+    return buf, len(r)
+
+
+def constwo_batch(ctx, pwds: Sequence, thr: float = 35., want_colscore: bool = False):
+    """g2g_constwo_batch <-> Ssrel::constwo (reference src/consreg.cc:438-450) on built pairs (operator.PwdM) whose two groups are
+    juxtaposed sons of one MSA: [ranges (n, 2) int32] per pair -- columns [left, right) --, with want_colscore
+    [(ranges, s float64[len])], s the score of every column.  ctx may be None only to have the arguments checked."""
+    L = lib()
+    n = len(pwds)
+    hs = (C.c_void_p * max(1, n))(*[p._h for p in pwds])
+    rng = (C.POINTER(_abi.Range) * max(1, n))()
+    nr = (C.c_int * max(1, n))()
+    st = (C.c_int * max(1, n))()
+    col = (_abi.c_f64p * max(1, n))() if want_colscore else None
+    rc = L.g2g_constwo_batch(ctx._h if ctx is not None else None, n, hs, float(thr), rng, nr, col, st)
+    if rc != 0:
+        raise G2GError("g2g_constwo_batch rc=%d: %s" % (rc, last_error()))
+    out = []
+    for k in range(n):
+        r = _take_ranges(rng[k], nr[k])
+        if want_colscore:
+            ln = pwds[k].problem.a.len
+            s = np.ctypeslib.as_array(col[k], shape=(ln,)).copy()
+            L.g2g_free(col[k])
+            out.append((r, s))
+        else:
+            out.append(r)
+    return out
+
+
+def conserved_regions(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None, dissim: bool = False) -> np.ndarray:
+    """g2g_consreg <-> Ssrel::consreg(msd, dissim) (reference src/consreg.cc:484-518): the columns of an MSA ((len, many) uint8
+    codes) that are conserved across EVERY branch of its weighting tree, as ranges (n, 2) int32 of columns [left, right); with
+    dissim the complement in [0, len) -- the ranges prrn's default pipeline hands to its refinement.  tree: a refine.KTree /
+    anything with left, right, parent (vol / cur are not read).  prm: the reference's localprm -- operator.AlnParam(u=3, v=10, u0=0,
+    u1=0, tgapf=1, scale=1, k1=7, ls=2, sh=100, banded=1, simmtx=<the reference's matrix number 1>).to_c()[0]."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    if codes.ndim != 2:
+        raise ValueError("codes must be (len, many)")
+    ln, many = codes.shape
+    nn = 2 * many - 1
+    arrs = [np.ascontiguousarray(getattr(tree, k), np.int32) for k in ("left", "right", "parent")]
+    vol = np.ascontiguousarray(getattr(tree, "vol", None) if getattr(tree, "vol", None) is not None else np.ones(nn), np.float64)
+    cur = np.ascontiguousarray(getattr(tree, "cur", None) if getattr(tree, "cur", None) is not None else np.ones(nn), np.float64)
+    t = _abi.Tree()
+    t.n_nodes = len(arrs[0])
+    t.left, t.right, t.parent = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in arrs)
+    t.vol, t.cur = vol.ctypes.data_as(_abi.c_f64p), cur.ctypes.data_as(_abi.c_f64p)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    if w is not None and len(w) != many:
+        raise ValueError("one weight per member")
+    out = C.POINTER(_abi.Range)()
+    nout = C.c_int(0)
+    rc = lib().g2g_consreg(ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
+                           None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(t), 1 if dissim else 0, C.byref(out), C.byref(nout))
+    if rc != 0:
+        raise G2GError("g2g_consreg rc=%d: %s" % (rc, last_error()))
+    return _take_ranges(out, nout.value)
+
+
+def ranges_intersect(a, b) -> np.ndarray:
+    """g2g_ranges_combine(dissim = 0) <-> cmnrng(a, b, 0) (reference src/css.cc:261-282), host only"""
+    ba, na = _range_array(a)
+    bb, nb = _range_array(b)
+    out = C.POINTER(_abi.Range)()
+    nout = C.c_int(0)
+    rc = lib().g2g_ranges_combine(ba, na, bb, nb, 0, 0, C.byref(out), C.byref(nout))
+    if rc != 0:
+        raise G2GError("g2g_ranges_combine rc=%d" % rc)
+    return _take_ranges(out, nout.value)
+
+
+def ranges_complement(a, length: int) -> np.ndarray:
+    """g2g_ranges_combine(dissim = 1) <-> complerng (css.cc:313-336) of the ranges a inside [0, length), host only"""
+    ba, na = _range_array(a)
+    out = C.POINTER(_abi.Range)()
+    nout = C.c_int(0)
+    rc = lib().g2g_ranges_combine(ba, na, None, 0, 1, int(length), C.byref(out), C.byref(nout))
+    if rc != 0:
+        raise G2GError("g2g_ranges_combine rc=%d" % rc)
+    return _take_ranges(out, nout.value)
