@@ -193,10 +193,10 @@ __device__ __forceinline__ void v6_incdelta(const bool on, const DH<NE> &h, lu32
 // newdelta (gfreq.cc:570-587) as a step function over the static entries of a t list
 struct ND6 { int kd; unsigned tg, tn; bool on; };
 // (LONG: some lane of the wave is about to store at or beyond the inline part)
-template <int NE, bool SCAN, bool LONG>
-__device__ __forceinline__ void nd6_step(ND6 &s, const DH<NE> &h, const int g, const unsigned key, lu32 *d1, lu32 *d2, lu32 *sink, const LS6 &W, const int I)
+// (nd6_step_sn: sn = nins of the entry that governs the static entry's glen, already looked up by the caller)
+template <bool LONG>
+__device__ __forceinline__ void nd6_step_sn(ND6 &s, const unsigned sn, const int g, lu32 *d1, lu32 *d2, lu32 *sink, const LS6 &W, const int I)
 {
-    const unsigned sn = dh_ent<NE, SCAN>(key, h, W, I) & 0xFFFFu;
     const bool emit = s.on && g >= 0 && sn > s.tn;
     const unsigned e = (s.tg << 16) | s.tn;
     if (LONG) {
@@ -209,6 +209,11 @@ __device__ __forceinline__ void nd6_step(ND6 &s, const DH<NE> &h, const int g, c
     s.tn = emit ? sn : s.tn;
     s.tg = emit ? (unsigned) (g + 1) : s.tg;
     s.on = s.on && g >= 0;
+}
+template <int NE, bool SCAN, bool LONG>
+__device__ __forceinline__ void nd6_step(ND6 &s, const DH<NE> &h, const int g, const unsigned key, lu32 *d1, lu32 *d2, lu32 *sink, const LS6 &W, const int I)
+{
+    nd6_step_sn<LONG>(s, dh_ent<NE, SCAN>(key, h, W, I) & 0xFFFFu, g, d1, d2, sink, W, I);
 }
 template <int NE>
 __device__ __forceinline__ void nd6_fin(const ND6 &s, const bool was_on, lu32 *d1, lu32 *d2, lu32 *sink, const LS6 &W, const int I)
@@ -268,12 +273,13 @@ struct B6 { Ring6 rs, rt; int os, ot, lens, lent, lenr; double rhf; };          
 // here is guarded by that length: slots between it and M are "behind the list" in every lane and add the same +0 that a lane
 // whose own list is shorter than the wave's has always added.  (With the length as a run-time guard inside the unrolled loops
 // the compiler kept all N slots in the kk loop and selected each one twice more on a loop-invariant "d < TA" mask.)
+// j: the stretched keys of the row list's slots, handed out (the a-side update of a diagonal H takes its nins from the d1 merge's).
 template <int M, int N, int NE, bool SCAN, bool RV>
 __device__ __forceinline__ double v6_xmerge(const DH<NE> &ha, const DH<NE> &hb, const unsigned (&dk)[N], const double (&dfq)[N], const double hf,
-                                            const B6 &B, const int lmax, const LS6 &W)
+                                            const B6 &B, const int lmax, const LS6 &W, unsigned (&j)[M])
 {
     static_assert(M <= N, "bucket beyond the register lists");
-    unsigned j[M], jh = 0;
+    unsigned jh = 0;
     double S[M], Sh = 0;
     if (RV) jh = dh_stretch<NE, SCAN>(0xFFFFu, ha, W, W.ia);
     V6_UNROLL
@@ -297,6 +303,48 @@ __device__ __forceinline__ double v6_xmerge(const DH<NE> &ha, const DH<NE> &hb, 
     V6_UNROLL
     for (int d = 0; d < M; ++d) g += S[d] * dfq[d];
     return g;
+}
+template <int M, int N, int NE, bool SCAN, bool RV>
+__device__ __forceinline__ double v6_xmerge(const DH<NE> &ha, const DH<NE> &hb, const unsigned (&dk)[N], const double (&dfq)[N], const double hf,
+                                            const B6 &B, const int lmax, const LS6 &W)
+{
+    unsigned j[M];
+    return v6_xmerge<M, N, NE, SCAN, RV>(ha, hb, dk, dfq, hf, B, lmax, W, j);
+}
+// The d1 / gnph / goph merges in ONE kk loop: each ring entry is read once and looked up in the three b heads -- three
+// independent chains -- and every sum is the one v6_xmerge makes, in its order.  D1 false: gnph and goph only (g1 comes back 0, j1
+// is not touched); three j / S sets of 12 or 16 slots do not fit the register file, two sets of 12 do.  j1: as j of v6_xmerge for
+// the d1 merge.
+template <int M, int N, int NE, bool SCAN, bool D1>
+__device__ __forceinline__ void v6_xmerge3(const DH<NE> &ha1, const DH<NE> &hb1, const DH<NE> &ha2, const DH<NE> &hb2, const DH<NE> &ha3, const DH<NE> &hb3,
+                                           const unsigned (&dk)[N], const double (&dfq)[N], const double hf, const B6 &B, const int lmax, const LS6 &W,
+                                           unsigned (&j1)[M], double &g1, double &g2, double &g3)
+{
+    static_assert(M <= N, "bucket beyond the register lists");
+    unsigned j2[M], j3[M];
+    double S1[M], S2[M], S3[M], Sh2 = 0, Sh3 = 0;
+    const unsigned jh2 = dh_stretch<NE, SCAN>(0xFFFFu, ha2, W, W.ia), jh3 = dh_stretch<NE, SCAN>(0xFFFFu, ha3, W, W.ia);
+    V6_UNROLL
+    for (int d = 0; d < M; ++d) {
+        if (D1) j1[d] = dh_stretch<NE, SCAN>(dk[d], ha1, W, W.ia);
+        j2[d] = dh_stretch<NE, SCAN>(dk[d] + 0x10000u, ha2, W, W.ia);
+        j3[d] = dh_stretch<NE, SCAN>(dk[d] + 0x10000u, ha3, W, W.ia);
+        S1[d] = S2[d] = S3[d] = 0;
+    }
+    for (int kk = lmax - 1; kk >= 0; --kk) {
+        const bool valid = kk < B.lens;
+        const SE6 e = se6_read(B.rs, B.os + (valid ? kk : 0));
+        const unsigned v1 = D1 ? dh_stretch<NE, SCAN>(e.key, hb1, W, W.ib) : 0u, v2 = dh_stretch<NE, SCAN>(e.key, hb2, W, W.ib), v3 = dh_stretch<NE, SCAN>(e.key, hb3, W, W.ib);
+        const unsigned i1 = valid ? v1 : 0u, i2 = valid ? v2 : 0u, i3 = valid ? v3 : 0u;
+        Sh2 = i2 >= jh2 ? e.f : Sh2;
+        Sh3 = i3 >= jh3 ? e.f : Sh3;
+        V6_UNROLL
+        for (int d = 0; d < M; ++d) { if (D1) S1[d] = i1 >= j1[d] ? e.f : S1[d]; S2[d] = i2 >= j2[d] ? e.f : S2[d]; S3[d] = i3 >= j3[d] ? e.f : S3[d]; }
+    }
+    g1 = 0; g2 = 0; g3 = 0;
+    g2 += Sh2 * hf; g3 += Sh3 * hf;
+    V6_UNROLL
+    for (int d = 0; d < M; ++d) { if (D1) g1 += S1[d] * dfq[d]; g2 += S2[d] * dfq[d]; g3 += S3[d] * dfq[d]; }
 }
 
 // ---- one cell by one lane ----------------------------------------------------------------------------------
@@ -389,21 +437,47 @@ __device__ __forceinline__ bool v6_cell_pf(const DevProb &P, const LS6 &W, const
     V6_STAMP(2)
 #ifndef V6_SKIP_X
     // ---- "X" merges: cf = the column's s list, df = a row list: diagonal part 1 (a.t, hd), horizontal gnp / gop (a.r, fl / hl)
+    unsigned jd[N];
     {
+        // merges that share one kk loop, per bucket: all three in the buckets of 4 and 8 slots, gnph and goph in the bucket of 12
+        // (two j / S sets of 12 slots are what three of 8 are), none in the N-slot bucket (the kernel would leave its registers)
+#ifdef V6_NO_XFUSE                                          // (diagnostic build: separate merges in every bucket)
+        constexpr int XFUSE4 = 0, XFUSE8 = 0, XFUSE12 = 0;
+#else
+        constexpr int XFUSE4 = 3, XFUSE8 = 3, XFUSE12 = 2;
+#endif
         int lmax = 0;
         while (__ballot(B.lens > lmax)) ++lmax;
         // the slots of the merges: the smallest of 4, 8, 12, N that holds the wave's longest t list -- one wave-uniform branch per
         // cell (TAt is a ballot count of v6_strip), outside the kk loops.  The SCAN instance (lists of nine entries and more) runs
         // all N slots: it never counts, and one form keeps its code small.
-#define V6_XMERGES(M) {                                                                                                          \
-        c.d1 = v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, false>(a_hd, b_hd, A.tk, A.tf, 0., B, lmax, W) * P.basic_gop;           \
-        c.gnph = v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, true>(a_fl, b_fl, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop;       \
-        c.goph = v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, true>(a_hl, b_hl, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop;       \
-        c.gnph2 = NOLL3 ? v6_xmerge<(M) < N ? (M) : N, N, NE, SCAN, true>(a_f2, b_f2, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop : 0; }
-        if (SCAN || (N > 12 && TAt > 12)) V6_XMERGES(N)
-        else if (N > 8 && TAt > 8) V6_XMERGES(12)
-        else if (TAt > 4) V6_XMERGES(8)
-        else V6_XMERGES(4)
+        // FUSE: 3: the first three merges share one kk loop (v6_xmerge3), 2: gnph and goph do, 0: none.  jd: the d1 merge's stretched
+        // keys, kept for the a-side update below (slots behind the bucket are behind every lane's list: never looked at, TAt is at
+        // most the bucket).
+#define V6_XMERGES(M, FUSE) {                                                                                                    \
+        constexpr int Mb = (M) < N ? (M) : N;                                                                                    \
+        unsigned j[Mb];                                                                                                          \
+        if ((FUSE) == 3) {                                                                                                       \
+            double g1, g2, g3;                                                                                                   \
+            v6_xmerge3<Mb, N, NE, SCAN, true>(a_hd, b_hd, a_fl, b_fl, a_hl, b_hl, A.tk, A.tf, A.rhf, B, lmax, W, j, g1, g2, g3); \
+            c.d1 = g1 * P.basic_gop; c.gnph = g2 * P.basic_gop; c.goph = g3 * P.basic_gop;                                       \
+        } else if ((FUSE) == 2) {                                                                                                \
+            double g1, g2, g3;                                                                                                   \
+            c.d1 = v6_xmerge<Mb, N, NE, SCAN, false>(a_hd, b_hd, A.tk, A.tf, 0., B, lmax, W, j) * P.basic_gop;                   \
+            v6_xmerge3<Mb, N, NE, SCAN, false>(a_hd, b_hd, a_fl, b_fl, a_hl, b_hl, A.tk, A.tf, A.rhf, B, lmax, W, j, g1, g2, g3); \
+            c.gnph = g2 * P.basic_gop; c.goph = g3 * P.basic_gop;                                                                \
+        } else {                                                                                                                 \
+            c.d1 = v6_xmerge<Mb, N, NE, SCAN, false>(a_hd, b_hd, A.tk, A.tf, 0., B, lmax, W, j) * P.basic_gop;                   \
+            c.gnph = v6_xmerge<Mb, N, NE, SCAN, true>(a_fl, b_fl, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop;                  \
+            c.goph = v6_xmerge<Mb, N, NE, SCAN, true>(a_hl, b_hl, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop;                  \
+        }                                                                                                                        \
+        c.gnph2 = NOLL3 ? v6_xmerge<Mb, N, NE, SCAN, true>(a_f2, b_f2, A.tk, A.tf, A.rhf, B, lmax, W) * P.basic_gop : 0;         \
+        V6_UNROLL                                                                                                                \
+        for (int d = 0; d < N; ++d) jd[d] = d < Mb ? j[d < Mb ? d : 0] : 0u; }
+        if (SCAN || (N > 12 && TAt > 12)) V6_XMERGES(N, 0)
+        else if (N > 8 && TAt > 8) V6_XMERGES(12, XFUSE12)
+        else if (TAt > 4) V6_XMERGES(8, XFUSE8)
+        else V6_XMERGES(4, XFUSE4)
 #undef V6_XMERGES
     }
 #endif
@@ -423,13 +497,19 @@ __device__ __forceinline__ bool v6_cell_pf(const DevProb &P, const LS6 &W, const
         for (int k = 0; k < N; ++k) {
             if (k < TAt) {
                 const int g = k < A.lt ? (int) (A.tk[k] >> 16) : -1;
+                // n_h looks a.t's keys up in a_hd, as the d1 merge has: jd[k] = (entry << 16) + key, and entry << 16 is nins << 16
+#ifndef V6_SKIP_X
+                const unsigned sn_h = (jd[k] - A.tk[k]) >> 16;
+#else
+                const unsigned sn_h = dh_ent<NE, SCAN>(A.tk[k], a_hd, W, W.ia) & 0xFFFFu;
+#endif
                 if (NE > 5 && __ballot(n_g.kd >= W.ia || n_h.kd >= W.ia || (NOLL3 && n_g2.kd >= W.ia))) {      // a result outgrows its inline part
                     nd6_step<NE, SCAN, true>(n_g, h_gs, g, A.tk[k], dg, g_d2, sink, W, W.ia);
-                    nd6_step<NE, SCAN, true>(n_h, a_hd, g, A.tk[k], dh, nul, sink, W, W.ia);
+                    nd6_step_sn<true>(n_h, sn_h, g, dh, nul, sink, W, W.ia);
                     if (NOLL3) nd6_step<NE, SCAN, true>(n_g2, h_gs2, g, A.tk[k], dg2, g2_d2, sink, W, W.ia);
                 } else {
                     nd6_step<NE, SCAN, false>(n_g, h_gs, g, A.tk[k], dg, g_d2, sink, W, W.ia);
-                    nd6_step<NE, SCAN, false>(n_h, a_hd, g, A.tk[k], dh, nul, sink, W, W.ia);
+                    nd6_step_sn<false>(n_h, sn_h, g, dh, nul, sink, W, W.ia);
                     if (NOLL3) nd6_step<NE, SCAN, false>(n_g2, h_gs2, g, A.tk[k], dg2, g2_d2, sink, W, W.ia);
                 }
             }
