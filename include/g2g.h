@@ -528,7 +528,7 @@ int        g2g_kmer_dist_from_counts_spec(const g2g_kmer_spec *sp, int npairs, c
  * step, cons2_ng / _nv / _hf / _pf (consreg.cc:170-406) by the PwdM's banded mode -- and a thresholded running sum over s gives
  * ranges of columns; the ranges of all divisions are intersected (cmnrng, src/css.cc:261-282).  The column scores and the scan
  * run on the GPU (csrc/g2g_consreg.hip: one workgroup per division), in the reference's order of double additions.
- * Not on this path: consregss / mayfuse (group fusing), Conserved1, findoutliers, refinement restricted to ranges.
+ * Not on this path: Conserved1, findoutliers, refinement restricted to ranges (the plan of it is g2g_refine_plan below).
  * (Entry points added without a change of g2g_abi_version.) */
 typedef struct { int32_t left, right; } g2g_range;
 
@@ -555,6 +555,72 @@ int g2g_consreg(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int l
    the intersection with empty pieces dropped (len is not read); dissim = 1: complerng, [0, len) without the ranges of a (b is not
    read).  *out malloc'ed (g2g_free). */
 int g2g_ranges_combine(const g2g_range *a, int na, const g2g_range *b, int nb, int dissim, int len, g2g_range **out, int *nout);
+
+/* ---- fused groups and the per-range refinement plan -------------------------------------------------------------------
+ * <-> ConservedT::mayfuse / testssrel / rearrange, Ssrel::consregss, Ssrel::consreg over a relation with groups (reference
+ * src/consreg.cc:452-464, 569-589, 667-711, 484-518) and what IterMsa::preprrn decides with them (src/prrn5.cc:794-823): subtrees
+ * of the weighting tree whose two sons are conserved from end to end are fused into groups, the unconserved column ranges are
+ * sought over the grouped relation, and inside every range the groups are fused again.  The fuse test walks the column scores
+ * of g2g_constwo_batch with another recurrence (scr += s; a positive scr becomes 0; the walk breaks where scr < fthr) on the GPU
+ * (g2g_mayfuse_kernel in csrc/g2g_consreg.hip: one workgroup per test).
+ * Not on this path: g2g_refine over the plan (grouped leaves, ranges), recalcpw of a fused tree, Conserved1, findoutliers.
+ * (Entry points added without a change of g2g_abi_version.) */
+typedef struct g2g_subset {         /* Subset (src/sets.h:27-31): group g holds member[start[g] .. start[g + 1])                  */
+    int32_t num, elms;              /* groups; members in all                                                                    */
+    int32_t *start, *member;        /* num + 1 and elms ints; malloc'ed when the library hands a subset out (g2g_subset_free)    */
+} g2g_subset;
+void g2g_subset_free(g2g_subset *s);
+typedef struct g2g_relation {       /* a subset and the tree over its groups (Ssrel: ss + ktree); release with g2g_relation_free  */
+    int32_t fused;                  /* 0: nothing fused -- the reference's NULL; the relation repeats the one that was given     */
+    g2g_subset ss;
+    int32_t n_nodes;                /* 2 * ss.num - 1: leaf g is group g, the other nodes in post-order, the root last           */
+    int32_t *left, *right, *parent; /* -1 where absent                                                                           */
+    int32_t *origin;                /* the node of the given tree each node was copied from (Knode fields are copies: vol, cur)  */
+    double  *vol, *cur;
+} g2g_relation;
+void g2g_relation_free(g2g_relation *r);
+typedef struct g2g_fuse_stats { int32_t tests, fused, launches, reserved; } g2g_fuse_stats;
+
+/* <-> ConservedT::mayfuse on n built pairs whose two groups are juxtaposed sons of equal length.  u, v: ALPRM::u, ::v (floats in
+   the reference; fthr = (VTYPE) -((2 u + v)) * a->sumwt * b->sumwt, consreg.cc:73).  fuse[i] 1: the walk reached the last column;
+   stop_col[i]: the column at which scr < fthr first held, -1 when fused.  Refusals as g2g_constwo_batch, all before the device
+   is asked for; a NULL context with good arguments is G2G_ERR_ARG.                                                              */
+int g2g_mayfuse_batch(g2g_ctx *ctx, int n, g2g_pwdm *const *pw, double u, double v, int *fuse, int *stop_col, int *status);
+
+/* <-> Ssrel::consregss on the columns [left, right) of an MSA (what restrange + consregss computes).  tree: the relation's tree,
+   its leaves 0 .. k - 1 are the relation's groups (groups NULL: the members themselves, k = many).  The tests run level by level:
+   round r holds the inner nodes whose two sons are leaves or were fused in earlier rounds -- the tests of the reference's post-
+   order walk, none else -- and is one g2g_mayfuse_batch on sons built by the level-1 builders.  Groups are numbered in leaf
+   post-order, left before right; a fused node hands its members over from left to right.  Everything fused: one group, a tree
+   of one node.  G2G_ERR_MODE: banded != 1, u0 > 0, tgapf != 1; G2G_ERR_ARG: a malformed tree or subset, an empty or out-of-bounds
+   range, many < 2.  stats may be NULL.                                                                                          */
+int g2g_consregss(g2g_ctx *ctx, const g2g_params *prm, int many, int len, const uint8_t *codes, const double *weight,
+                  const g2g_tree *tree, const g2g_subset *groups, int left, int right, g2g_relation *out, g2g_fuse_stats *stats);
+
+/* <-> Ssrel::consreg over a relation with groups: the 2 num - 3 divisions of the tree over the groups in Randiv's numbering
+   (num = 2: the one division), member lists expanded through the groups (bin2lst2g, src/randiv.cc:88-100).  groups NULL:
+   g2g_consreg (but two members are served).                                                                                     */
+int g2g_consreg_groups(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                       const double *weight, const g2g_tree *tree, const g2g_subset *groups, int dissim, g2g_range **out, int *nout);
+
+/* What preprrn decides before any Prrn is built, from the unrefined MSA and its weighting tree (g2g_ktree_from_msa): the whole-MSA
+   relation (consregss), the attack ranges (consreg(DISSIM) over it, ascending), and per range its own relation (consregss inside
+   the range, over the whole-MSA relation; origin names nodes of `whole`) and whether it touches column 0 / len -- where exgl /
+   exgr are kept (prrn5.cc:814-815).  The ranges' fuse rounds share launches.  status G2G_PLAN_NOTHING_TO_REFINE: the whole-MSA
+   relation has fewer than two groups; there are no ranges then.  Release with g2g_refine_plan_free.                             */
+#define G2G_PLAN_OK 0
+#define G2G_PLAN_NOTHING_TO_REFINE 1
+typedef struct g2g_refine_plan_t {
+    int32_t status, nranges;
+    g2g_relation whole;
+    g2g_range *ranges;
+    int32_t *at_left, *at_right;
+    g2g_relation *range_rel;
+    g2g_fuse_stats stats;           /* over the whole call; launches: g2g_mayfuse_batch calls                                   */
+} g2g_refine_plan_t;
+int  g2g_refine_plan(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                     const double *weight, const g2g_tree *tree, g2g_refine_plan_t *out);
+void g2g_refine_plan_free(g2g_refine_plan_t *p);
 
 #ifdef __cplusplus
 }

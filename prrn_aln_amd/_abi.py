@@ -89,6 +89,27 @@ class Range(C.Structure):
     _fields_ = [("left", C.c_int32), ("right", C.c_int32)]
 
 
+class Subset(C.Structure):
+    """g2g_subset: group g holds member[start[g] .. start[g + 1])"""
+    _fields_ = [("num", C.c_int32), ("elms", C.c_int32), ("start", c_i32p), ("member", c_i32p)]
+
+
+class Relation(C.Structure):
+    """g2g_relation: a subset and the tree over its groups (arrays owned by the library: g2g_relation_free)"""
+    _fields_ = [("fused", C.c_int32), ("ss", Subset), ("n_nodes", C.c_int32), ("left", c_i32p), ("right", c_i32p), ("parent", c_i32p),
+                ("origin", c_i32p), ("vol", c_f64p), ("cur", c_f64p)]
+
+
+class FuseStats(C.Structure):
+    _fields_ = [("tests", C.c_int32), ("fused", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RefinePlan(C.Structure):
+    """g2g_refine_plan_t (g2g_refine_plan_free)"""
+    _fields_ = [("status", C.c_int32), ("nranges", C.c_int32), ("whole", Relation), ("ranges", C.POINTER(Range)),
+                ("at_left", c_i32p), ("at_right", c_i32p), ("range_rel", C.POINTER(Relation)), ("stats", FuseStats)]
+
+
 class KmerParams(C.Structure):
     """g2g_kmer_params: molecule, word length and DistMes of g2g_kmer_dist_batch (0 / -1: the reference's defaults)"""
     _fields_ = [("molc", C.c_int32), ("k", C.c_int32), ("measure", C.c_int32), ("reserved", C.c_int32)]

@@ -97,6 +97,20 @@ def lib():
     L.g2g_consreg.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_double, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
                               C.c_int, C.POINTER(RP), C.POINTER(C.c_int)]
     L.g2g_ranges_combine.argtypes = [RP, C.c_int, RP, C.c_int, C.c_int, C.c_int, C.POINTER(RP), C.POINTER(C.c_int)]
+    L.g2g_mayfuse_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int)]
+    L.g2g_consregss.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
+                                C.POINTER(_abi.Subset), C.c_int, C.c_int, C.POINTER(_abi.Relation), C.POINTER(_abi.FuseStats)]
+    L.g2g_consreg_groups.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_double, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
+                                     C.POINTER(_abi.Subset), C.c_int, C.POINTER(RP), C.POINTER(C.c_int)]
+    L.g2g_refine_plan.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_double, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
+                                  C.POINTER(_abi.RefinePlan)]
+    L.g2g_relation_free.restype = None
+    L.g2g_relation_free.argtypes = [C.POINTER(_abi.Relation)]
+    L.g2g_subset_free.restype = None
+    L.g2g_subset_free.argtypes = [C.POINTER(_abi.Subset)]
+    L.g2g_refine_plan_free.restype = None
+    L.g2g_refine_plan_free.argtypes = [C.POINTER(_abi.RefinePlan)]
     bind_level1(L)
     _lib = L
     return L

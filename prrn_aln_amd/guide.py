@@ -12,6 +12,7 @@ calls raise."""
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass, field
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -329,3 +330,156 @@ def ranges_complement(a, length: int) -> np.ndarray:
     if rc != 0:
         raise G2GError("g2g_ranges_combine rc=%d" % rc)
     return _take_ranges(out, nout.value)
+
+
+# ---- fused groups and the per-range refinement plan (what prrn's default run decides before it refines) -----------------------------
+@dataclass
+class Relation:
+    """A subset and the tree over its groups (the reference's Ssrel: ss + ktree).  groups[g]: int32 members of group g in the
+    reference's order; leaf g of the tree is group g; origin[k]: the node of the given tree node k was copied from."""
+    fused: bool
+    groups: List[np.ndarray]
+    left: np.ndarray
+    right: np.ndarray
+    parent: np.ndarray
+    origin: np.ndarray
+    vol: np.ndarray
+    cur: np.ndarray
+
+
+@dataclass
+class FuseStats:
+    tests: int = 0
+    fused: int = 0
+    launches: int = 0
+
+
+@dataclass
+class RefinePlan:
+    """nothing_to_refine: the whole-MSA relation has fewer than two groups.  ranges (n, 2) int32 ascending; at_left / at_right: the
+    range touches column 0 / len (where prrn keeps exgl / exgr); relations[i]: the range's own relation over `whole`."""
+    nothing_to_refine: bool
+    whole: Relation
+    ranges: np.ndarray
+    at_left: np.ndarray
+    at_right: np.ndarray
+    relations: List[Relation] = field(default_factory=list)
+    stats: FuseStats = field(default_factory=FuseStats)
+
+
+def _tree_struct(tree):
+    arrs = [np.ascontiguousarray(getattr(tree, k), np.int32) for k in ("left", "right", "parent")]
+    nn = len(arrs[0])
+    vol = np.ascontiguousarray(getattr(tree, "vol", None) if getattr(tree, "vol", None) is not None else np.ones(nn), np.float64)
+    cur = np.ascontiguousarray(getattr(tree, "cur", None) if getattr(tree, "cur", None) is not None else np.ones(nn), np.float64)
+    if not (len(arrs[1]) == len(arrs[2]) == len(vol) == len(cur) == nn):
+        raise ValueError("the tree's arrays must have one length")
+    t = _abi.Tree()
+    t.n_nodes = nn
+    t.left, t.right, t.parent = (a.ctypes.data_as(C.POINTER(C.c_int32)) for a in arrs)
+    t.vol, t.cur = vol.ctypes.data_as(_abi.c_f64p), cur.ctypes.data_as(_abi.c_f64p)
+    return t, (arrs, vol, cur)
+
+
+def _subset_struct(groups):
+    if groups is None:
+        return None, None
+    start = np.zeros(len(groups) + 1, np.int32)
+    start[1:] = np.cumsum([len(g) for g in groups])
+    member = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32).reshape(-1) for g in groups]) if len(groups) else np.zeros(0, np.int32), np.int32)
+    s = _abi.Subset()
+    s.num, s.elms = len(groups), len(member)
+    s.start, s.member = start.ctypes.data_as(_abi.c_i32p), member.ctypes.data_as(_abi.c_i32p)
+    return s, (start, member)
+
+
+def _msa_args(codes, weight):
+    codes = np.ascontiguousarray(codes, np.uint8)
+    if codes.ndim != 2:
+        raise ValueError("codes must be (len, many)")
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    if w is not None and len(w) != codes.shape[1]:
+        raise ValueError("one weight per member")
+    return codes, w
+
+
+def _take_relation(r: "_abi.Relation") -> Relation:
+    i32 = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n and p else np.zeros(0, np.int32)
+    f64 = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n and p else np.zeros(0, np.float64)
+    start, member = i32(r.ss.start, r.ss.num + 1), i32(r.ss.member, r.ss.elms)
+    nn = r.n_nodes
+    return Relation(bool(r.fused), [member[start[g]:start[g + 1]].copy() for g in range(r.ss.num)], i32(r.left, nn), i32(r.right, nn),
+                    i32(r.parent, nn), i32(r.origin, nn), f64(r.vol, nn), f64(r.cur, nn))
+
+
+def may_fuse_batch(ctx, pwds: Sequence, u: float = 3., v: float = 10.) -> Tuple[np.ndarray, np.ndarray]:
+    """g2g_mayfuse_batch <-> ConservedT::mayfuse (reference src/consreg.cc:452-464) on built pairs (operator.PwdM) whose two groups
+    are juxtaposed sons of one MSA: (fuse int32[n] 0 / 1, stop_col int32[n]: the column at which the walk broke, -1 when fused).
+    ctx may be None only to have the arguments checked."""
+    n = len(pwds)
+    hs = (C.c_void_p * max(1, n))(*[p._h for p in pwds])
+    fz = (C.c_int * max(1, n))()
+    sc = (C.c_int * max(1, n))()
+    st = (C.c_int * max(1, n))()
+    rc = lib().g2g_mayfuse_batch(ctx._h if ctx is not None else None, n, hs, float(u), float(v), fz, sc, st)
+    if rc != 0:
+        raise G2GError("g2g_mayfuse_batch rc=%d: %s" % (rc, last_error()))
+    return np.array(fz[:n], np.int32), np.array(sc[:n], np.int32)
+
+
+def fuse_groups(ctx, codes: np.ndarray, tree, prm: "_abi.Params", groups=None, left: int = 0, right=None, weight=None):
+    """g2g_consregss <-> Ssrel::consregss (reference src/consreg.cc:692-711) on the columns [left, right) of an MSA: subtrees of
+    `tree` whose two sons are conserved from end to end are fused.  tree: over the groups (`groups`: a list of member lists, None =
+    the members themselves).  Returns (Relation, FuseStats); Relation.fused False: nothing fused, the given relation again."""
+    codes, w = _msa_args(codes, weight)
+    ln, many = codes.shape
+    t, keep_t = _tree_struct(tree)
+    s, keep_s = _subset_struct(groups)
+    out, stats = _abi.Relation(), _abi.FuseStats()
+    rc = lib().g2g_consregss(ctx._h if ctx is not None else None, C.byref(prm), many, ln, codes.ctypes.data_as(_abi.c_u8p),
+                             None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(t), None if s is None else C.byref(s),
+                             int(left), ln if right is None else int(right), C.byref(out), C.byref(stats))
+    if rc != 0:
+        raise G2GError("g2g_consregss rc=%d: %s" % (rc, last_error()))
+    rel = _take_relation(out)
+    lib().g2g_relation_free(C.byref(out))
+    return rel, FuseStats(stats.tests, stats.fused, stats.launches)
+
+
+def conserved_regions_groups(ctx, codes: np.ndarray, tree, prm: "_abi.Params", groups=None, thr: float = 35., weight=None, dissim: bool = False) -> np.ndarray:
+    """g2g_consreg_groups <-> Ssrel::consreg over a relation with groups: conserved_regions with the leaves of `tree` standing for
+    `groups` (a list of member lists; None: conserved_regions itself)."""
+    codes, w = _msa_args(codes, weight)
+    ln, many = codes.shape
+    t, keep_t = _tree_struct(tree)
+    s, keep_s = _subset_struct(groups)
+    out = C.POINTER(_abi.Range)()
+    nout = C.c_int(0)
+    rc = lib().g2g_consreg_groups(ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
+                                  None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(t), None if s is None else C.byref(s),
+                                  1 if dissim else 0, C.byref(out), C.byref(nout))
+    if rc != 0:
+        raise G2GError("g2g_consreg_groups rc=%d: %s" % (rc, last_error()))
+    return _take_ranges(out, nout.value)
+
+
+def refine_plan(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None) -> RefinePlan:
+    """g2g_refine_plan <-> what IterMsa::preprrn decides before it refines (reference src/prrn5.cc:794-823): the fused groups of the
+    whole MSA, the unconserved ranges over them, and every range's own groups and tree."""
+    codes, w = _msa_args(codes, weight)
+    ln, many = codes.shape
+    t, keep_t = _tree_struct(tree)
+    out = _abi.RefinePlan()
+    rc = lib().g2g_refine_plan(ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
+                               None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(t), C.byref(out))
+    if rc != 0:
+        raise G2GError("g2g_refine_plan rc=%d: %s" % (rc, last_error()))
+    n = out.nranges
+    rng = np.zeros((n, 2), np.int32)
+    if n:
+        rng[:] = np.ctypeslib.as_array(C.cast(out.ranges, C.POINTER(C.c_int32)), shape=(2 * n,)).reshape(-1, 2)
+    i32 = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.int32)
+    plan = RefinePlan(out.status == 1, _take_relation(out.whole), rng, i32(out.at_left), i32(out.at_right),
+                      [_take_relation(out.range_rel[i]) for i in range(n)], FuseStats(out.stats.tests, out.stats.fused, out.stats.launches))
+    lib().g2g_refine_plan_free(C.byref(out))
+    return plan
