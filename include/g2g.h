@@ -528,7 +528,7 @@ int        g2g_kmer_dist_from_counts_spec(const g2g_kmer_spec *sp, int npairs, c
  * step, cons2_ng / _nv / _hf / _pf (consreg.cc:170-406) by the PwdM's banded mode -- and a thresholded running sum over s gives
  * ranges of columns; the ranges of all divisions are intersected (cmnrng, src/css.cc:261-282).  The column scores and the scan
  * run on the GPU (csrc/g2g_consreg.hip: one workgroup per division), in the reference's order of double additions.
- * Not on this path: Conserved1, findoutliers, refinement restricted to ranges (the plan of it is g2g_refine_plan below).
+ * Not on this path: Conserved1, findoutliers (refinement restricted to ranges: g2g_refine_plan and g2g_refine_planned below).
  * (Entry points added without a change of g2g_abi_version.) */
 typedef struct { int32_t left, right; } g2g_range;
 
@@ -563,7 +563,7 @@ int g2g_ranges_combine(const g2g_range *a, int na, const g2g_range *b, int nb, i
  * sought over the grouped relation, and inside every range the groups are fused again.  The fuse test walks the column scores
  * of g2g_constwo_batch with another recurrence (scr += s; a positive scr becomes 0; the walk breaks where scr < fthr) on the GPU
  * (g2g_mayfuse_kernel in csrc/g2g_consreg.hip: one workgroup per test).
- * Not on this path: g2g_refine over the plan (grouped leaves, ranges), recalcpw of a fused tree, Conserved1, findoutliers.
+ * The plan is run by g2g_refine_planned below.  Not on this path: recalcpw of a fused tree, Conserved1, findoutliers.
  * (Entry points added without a change of g2g_abi_version.) */
 typedef struct g2g_subset {         /* Subset (src/sets.h:27-31): group g holds member[start[g] .. start[g + 1])                  */
     int32_t num, elms;              /* groups; members in all                                                                    */
@@ -621,6 +621,56 @@ typedef struct g2g_refine_plan_t {
 int  g2g_refine_plan(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
                      const double *weight, const g2g_tree *tree, g2g_refine_plan_t *out);
 void g2g_refine_plan_free(g2g_refine_plan_t *p);
+
+/* ---- g2g_refine over the plan: prrn's default refinement (local_thr = 35) ------------------------------------------------
+ * <-> the loop of IterMsa::preprrn over the attack ranges (reference src/prrn5.cc:806-818): one Prrn (:688-781) per range, from
+ * the LAST range to the first, on the columns [left, right) of the current MSA and over plan->range_rel[r] (url = trl ? trl :
+ * srl).  A range's result replaces its columns and may be longer or shorter; the ranges still to come lie to its left, so their
+ * coordinates stay valid.  A range whose relation has fewer than two groups is skipped and draws nothing (Prrn::Prrn, num <= 1).
+ * Per range the loop is g2g_refine's (the two entry points share it) with groups for leaves: cycle = 2 num - 3 (two groups: the one
+ * division, once), a division's sides are the member lists expanded through the subset, each group in its own member order
+ * (bin2lst2g, src/randiv.cc:88-100), larger side first by member count (totalNoSeq).  In the matrix form a fused group is a set
+ * of columns of the matrix that always travel together.
+ *   prm    : the parameters of the DPs (the reference's alnprm).
+ *   plan   : NULL: the call makes it with g2g_refine_plan(ctx, prm, thr, ...) -- with the DPs' parameters (needs a context).  The
+ *            reference decides its plan with parameters of its own (localprm and similarity matrix number 1, see g2g_consreg):
+ *            a caller after the reference's run makes the plan with those and passes it.  Given, it is taken as it is (thr
+ *            is not read) after validation -- every subset partitions the members, every tree has 2 num - 1 nodes and is checked
+ *            as g2g_refine checks its tree, the ranges ascend, are disjoint and lie inside [0, len), origin is in range: else
+ *            G2G_ERR_ARG.  With a plan and opts->scorer, ctx may be NULL.  G2G_PLAN_NOTHING_TO_REFINE, or no ranges: the input
+ *            comes back unchanged with zero steps, G2G_OK.
+ *   weight : msd->weight as phyl_pwt leaves it (many doubles; for the tree of g2g_ktree_from_msa: vol of the leaves), as for
+ *            g2g_refine_plan.  A member of a fused group enters a builder as Ssrel::takeapart -> Seq::extseq(.., the group's vol)
+ *            (src/consreg.cc:598-625) and Prrn::gather / aggregate leave it: weight[m] / vol[group], times what calcfact gives the
+ *            group where the side holds several groups; a single member 1, times the same.  NULL: an MSA without weights -- a
+ *            side made of one fused group has none, members of a side of several groups carry calcfact's factor alone.
+ *   seed   : McRand (src/randiv.cc:34-53) draws rand() when the seed is 1 and then calls srand() on it: the second Prrn of a run
+ *            starts from the rand() state the first one left.  One restated glibc generator serves the whole call.
+ *   opts   : as for g2g_refine; maxitr, window, window_min (its default by the RANGE's length), scorer, on_accept (member lists,
+ *            expanded) and exchange / world > 1 apply per range.
+ *   steps  : the ranges' steps one after the other in processing order (last range first); branch is a node of that range's
+ *            relation tree.  rstat: one entry per range of the plan in the plan's order, skipped ranges with nsteps = 0 (g2g_free;
+ *            both may be NULL).  stats sums over the ranges.
+ * G2G_ERR_MODE: tgapf != 1, u0 > 0, banded != 1 (as the plan; with tgapf = 1 the exgl / exgr switch of prrn5.cc:814-815 changes
+ * nothing the DP reads: at_left / at_right are carried into rstat and otherwise unused); a leaf group without any residue inside
+ * its range (g2g_last_error names the range and the group).  All refusals come before any scoring.
+ * Not on this path: recycle > 1 (the caller builds a new tree and calls again); initsp / pairsum_ss over a relation with subsets
+ * and recalcpw of a fused tree (the trajectory reads neither; gain is the difference the reference prints); best_of_n,
+ * Conserved1, findoutliers.  (Entry point added without a change of g2g_abi_version.) */
+typedef struct g2g_refine_range_stat {
+    int32_t range, left, right;        /* index into plan->ranges; the columns before refinement */
+    int32_t groups, cycle;
+    int32_t first_step, nsteps;        /* slice of steps[] */
+    int32_t divisions, accepted;       /* divisions = the reference's countaln of this Prrn */
+    int32_t out_left, out_right;       /* the range's columns in the MSA as it stood when the range was done */
+    int32_t at_left, at_right, reserved;
+    double  gain;                      /* sum of the accepted deltas = sps - initsp of this Prrn */
+} g2g_refine_range_stat;
+int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                       const double *weight, const g2g_tree *tree, const g2g_refine_plan_t *plan,
+                       const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len,
+                       g2g_refine_step **steps, int *nsteps, g2g_refine_range_stat **rstat, int *nrstat,
+                       g2g_refine_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,14 @@ class RefineStats(C.Structure):
                 ("divisions_wasted", C.c_int32), ("wait_timeouts", C.c_int32), ("recovered_dps", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RefineRangeStat(C.Structure):
+    """g2g_refine_range_stat: one range of g2g_refine_planned"""
+    _fields_ = [("range", C.c_int32), ("left", C.c_int32), ("right", C.c_int32), ("groups", C.c_int32), ("cycle", C.c_int32),
+                ("first_step", C.c_int32), ("nsteps", C.c_int32), ("divisions", C.c_int32), ("accepted", C.c_int32),
+                ("out_left", C.c_int32), ("out_right", C.c_int32), ("at_left", C.c_int32), ("at_right", C.c_int32),
+                ("reserved", C.c_int32), ("gain", C.c_double)]
+
+
 def _ptr(arr: np.ndarray, typ):
     return arr.ctypes.data_as(typ)
 

@@ -105,6 +105,10 @@ def lib():
                                      C.POINTER(_abi.Subset), C.c_int, C.POINTER(RP), C.POINTER(C.c_int)]
     L.g2g_refine_plan.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_double, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
                                   C.POINTER(_abi.RefinePlan)]
+    L.g2g_refine_planned.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_double, C.c_int, C.c_int, _abi.c_u8p, _abi.c_f64p, C.POINTER(_abi.Tree),
+                                     C.POINTER(_abi.RefinePlan), C.POINTER(_abi.RefineOpts), C.POINTER(_abi.c_u8p), C.POINTER(C.c_int),
+                                     C.POINTER(C.POINTER(_abi.RefineStep)), C.POINTER(C.c_int), C.POINTER(C.POINTER(_abi.RefineRangeStat)),
+                                     C.POINTER(C.c_int), C.POINTER(_abi.RefineStats)]
     L.g2g_relation_free.restype = None
     L.g2g_relation_free.argtypes = [C.POINTER(_abi.Relation)]
     L.g2g_subset_free.restype = None

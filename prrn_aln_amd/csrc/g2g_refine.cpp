@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <stdarg.h>
 #include <string.h>
 #include <cmath>
 #include <string>
@@ -31,7 +32,20 @@
 #include "../../include/g2g.h"
 #include "g2g_internal.h"
 
+extern "C" void g2g_ctx_counters(const g2g_ctx *c, long long out[4]);
+
 namespace {
+
+void rf_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+void rf_err(const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g2g_set_error("%s", buf);
+}
 
 const uint8_t GAP = 1;
 const double FEPS = 1.0e-7;                                   // reference src/cmn.h:54
@@ -67,12 +81,12 @@ struct GlibcRand {
     int rand_() { return (int) (next() >> 1); }
 };
 
-// mixed congruential generator over [0, 2^p), src/randiv.cc:34-56, randiv.h:36-47
+// mixed congruential generator over [0, 2^p), src/randiv.cc:34-56, randiv.h:36-47.  libc is the process's rand() state in the
+// reference: a second Prrn of one run draws its seed from what the first one left there, so the caller owns it
 struct McRand {
     uint64_t mod, coef, val;
-    McRand(int p, int rn)
+    McRand(int p, int rn, GlibcRand &libc)
     {
-        GlibcRand libc;
         mod = (uint64_t) 1 << p;
         if (rn == 0) { coef = 1; val = mod - 1; return; }
         const int v = rn == 1 ? libc.rand_() : rn;
@@ -240,27 +254,69 @@ void free_division(Division &d)
     d.pw = 0; d.ga = d.gb = 0;
 }
 
-}   // namespace
-
-extern "C" void g2g_ctx_counters(const g2g_ctx *c, long long out[4]);
-
-extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len, const uint8_t *codes, const g2g_tree *tree,
-                          const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len, g2g_refine_step **steps, int *nsteps,
-                          g2g_refine_stats *stats)
+// the caller's options with the defaults filled in; window_min <= 0 stays: the loop decides it by the length of what it refines
+int fill_opts(const g2g_refine_opts *opts, g2g_refine_opts &O, const char *who)
 {
-    if (!prm || !codes || !tree || !out_codes || !out_len || many < 2 || len < 1) return G2G_ERR_ARG;
-    if (!ctx && !(opts && opts->scorer)) return G2G_ERR_ARG;               // the DPs run on the GPU unless the caller scores them
-    if (tree->n_nodes != 2 * many - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
-        g2g_set_error("%s", "g2g_refine: the tree must have 2 * many - 1 nodes (leaves 0 .. many - 1 = the members)");
-        return G2G_ERR_ARG;
-    }
-    if (const char *why = check_tree(tree, many)) { g2g_set_error("g2g_refine: malformed tree: %s", why); return G2G_ERR_ARG; }
-    g2g_refine_opts O;
     memset(&O, 0, sizeof O);
     if (opts) O = *opts;
     if (O.seed == 0) O.seed = 1;
     if (O.maxitr <= 0) O.maxitr = 10;
     if (O.window <= 0) O.window = 32;
+    if (O.world <= 0) { O.world = 1; O.rank = 0; }
+    if (O.slot_cap <= 0) O.slot_cap = 4096;
+    if (O.exchange && O.world > 1 && (O.rank < 0 || O.rank >= O.world)) { g2g_set_error("%s: rank outside [0, world)", who); return G2G_ERR_ARG; }
+    return G2G_OK;
+}
+
+// What one Prrn refines over (Prrn::Prrn, src/prrn5.cc:688-781): the leaves of T are GROUPS of members that move as one block
+// (group[g]: columns of the matrix, in the subset's order); g2g_refine's relation has every member as its own group.
+// weight: msd->weight (one per member) or NULL, read for groups of two and more members only.
+struct Rel {
+    Tree T;
+    std::vector<std::vector<int>> group;
+    const double *weight;
+};
+
+// The weights one side of a division enters its builder with (Prrn::gather, src/prrn5.cc:452-484).  takeapart made every group by
+// Seq::extseq(.., nfact = the group's vol) (src/consreg.cc:598-625, src/seq.cc:1141-1150): a single member 1, else weight[m] / vol.
+// A side of ONE group is that group itself (aliaseq); a side of several is aggregate (src/mgaps.cc:305-317): the group's own
+// weights times wlst[group] = what calcfact gave the group, or wlst[group] alone where the MSA has no weights.
+// false: no weights at all (a group of several members of an MSA without weights, standing alone).
+bool side_weights(const Rel &R, const std::vector<int> &groups, const std::vector<double> &wlst, std::vector<double> &out)
+{
+    out.clear();
+    if (groups.size() == 1) {
+        const int g = groups[0];
+        const std::vector<int> &mem = R.group[(size_t) g];
+        if (mem.size() == 1) { out.push_back(1.0); return true; }
+        if (!R.weight) return false;
+        for (int m : mem) out.push_back(R.weight[m] / R.T.vol[g]);
+        return true;
+    }
+    for (int g : groups) {
+        const std::vector<int> &mem = R.group[(size_t) g];
+        const double wt = wlst[(size_t) g];
+        for (int m : mem) {
+            if (!R.weight) out.push_back(wt);
+            else out.push_back((mem.size() == 1 ? 1.0 : R.weight[m] / R.T.vol[g]) * wt);
+        }
+    }
+    return true;
+}
+
+struct LoopResult {
+    int countaln;                                             // Prrn::countaln (src/prrn5.cc:664): the loop variable where rir left its loop
+    int accepted;
+    double gain;                                              // the accepted deltas in order: sps - initsp
+};
+
+// Prrn::rir over one relation (src/prrn5.cc:633-666), DPs batched in windows: M is refined in place, the steps are appended to
+// log, S is added to.  libc: the rand() state the McRand seeds itself from and leaves changed.
+int refine_loop(g2g_ctx *ctx, const g2g_params *prm, g2g_refine_opts O, const Rel &R, GlibcRand &libc, Msa &M,
+                std::vector<g2g_refine_step> &log, g2g_refine_stats &S, LoopResult &res, double t_base, const char *who)
+{
+    const std::string W(who);
+    const int many = M.many, num = R.T.nleaf;
     // The first window after an accepted move.  A window costs ONE DP latency whatever its size while the GPU has room (a 5e6-cell
     // DP takes 50-90 ms alone and sixteen of them take 60-100 ms together: a DP is a chain of rows + columns dependent steps), so
     // with large DPs it pays to start wide and throw the speculation behind an acceptance away; small DPs start at 2.
@@ -268,31 +324,22 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
     //  accepted division: with one division in six accepted, sixteen at a time is where the 256 x 1024 refinement is fastest -- 96.7 s
     //  against 104.3 s for windows of 8-16 and 97.9 s for 16-32; small MSAs accept more often and start at four: the 48 x 300 family, 38 %
     //  accepted, 8.5 s against 11.1 s from two and 8.7 s from eight)
-    if (O.window_min <= 0) O.window_min = (long long) len * len >= (1LL << 22) ? 16 : 4;
+    if (O.window_min <= 0) O.window_min = (long long) M.len * M.len >= (1LL << 22) ? 16 : 4;
     if (O.window_min > O.window) O.window_min = O.window;
-    if (O.world <= 0) { O.world = 1; O.rank = 0; }
-    if (O.slot_cap <= 0) O.slot_cap = 4096;
     const bool sharded = O.exchange && O.world > 1;
-    if (sharded && (O.rank < 0 || O.rank >= O.world)) { g2g_set_error("%s", "g2g_refine: rank outside [0, world)"); return G2G_ERR_ARG; }
     const int slot_ints = 9 + 2 * O.slot_cap;
 
-    Tree T;
-    T.nn = tree->n_nodes; T.nleaf = many; T.left = tree->left; T.right = tree->right; T.parent = tree->parent; T.vol = tree->vol; T.cur = tree->cur;
-    // Randiv in TREEDIV mode (src/randiv.cc:158-178,217-226)
-    const int cycle = 2 * many - 3;
+    const Tree &T = R.T;
+    // Randiv in TREEDIV mode (src/randiv.cc:158-178,217-226); two groups: cycle 1, a generator over [0, 1) that hands out branch 0
+    const int cycle = 2 * num - 3;
     int p2 = 0;
     for (int x = 1; x < cycle; x <<= 1) ++p2;
-    McRand mcr(p2, O.seed);
+    McRand mcr(p2, O.seed, libc);
     auto next_branch = [&]() { for (;;) { const int r = mcr.next(); if (r < cycle) return r; } };
 
-    Msa M;
-    M.len = len; M.many = many; M.c.assign(codes, codes + (size_t) len * many);
-    std::vector<g2g_refine_step> log;
-    g2g_refine_stats S;
-    memset(&S, 0, sizeof S);
+    const size_t log0 = log.size();
+    res.countaln = 0; res.accepted = 0; res.gain = 0;
     int rc_all = G2G_OK;
-    long long cnt0[4] = {0, 0, 0, 0};
-    if (ctx) g2g_ctx_counters(ctx, cnt0);
 
     const int maxi = O.maxitr * cycle;
     int nrep = 0, it = 0, win = O.window_min;
@@ -323,21 +370,25 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
                 Division &d = D[k];
                 d.branch = pending[k];
                 T.leaves(d.branch, inside);
-                std::vector<char> in((size_t) many, 0);
-                for (int l : inside) in[l] = 1;
+                std::vector<char> in((size_t) num, 0);
+                size_t nin = 0, nout = 0;
+                for (int l : inside) { in[l] = 1; nin += R.group[(size_t) l].size(); }
                 std::vector<int> outside;
-                for (int i = 0; i < many; ++i) if (!in[i]) outside.push_back(i);
-                // bin2lst2 + the swap of Prrn::divideseq: (larger group, smaller group)
-                if (outside.size() < inside.size()) { d.la = inside; d.lb = outside; } else { d.la = outside; d.lb = inside; }
+                for (int i = 0; i < num; ++i) if (!in[i]) { outside.push_back(i); nout += R.group[(size_t) i].size(); }
+                // bin2lst2 + the swap of Prrn::divideseq by totalNoSeq: (larger side, smaller side), each a list of groups; the member
+                // lists are the groups in ascending order, each handing over its members in its own order (bin2lst2g)
+                const std::vector<int> &ga = nout < nin ? inside : outside, &gb = nout < nin ? outside : inside;
+                d.la.clear(); d.lb.clear();
+                for (int g : ga) d.la.insert(d.la.end(), R.group[(size_t) g].begin(), R.group[(size_t) g].end());
+                for (int g : gb) d.lb.insert(d.lb.end(), R.group[(size_t) g].begin(), R.group[(size_t) g].end());
                 d.pwt = T.calcfact(d.branch, w);
                 split_columns(M, d);
                 if (d.ra == M.len && d.rb == M.len) { d.skip = true; continue; }     // nothing to re-align (src/prrn5.cc:497-498,518-521)
-                // a group of one member is the member itself in the reference (aliaseq): weight 1
+                // a side of one member is the member itself in the reference (aliaseq): weight 1
                 std::vector<double> wa, wb;
-                for (int l : d.la) wa.push_back(d.la.size() > 1 ? w[l] : 1.0);
-                for (int l : d.lb) wb.push_back(d.lb.size() > 1 ? w[l] : 1.0);
-                d.ga = g2g_group_create(ctx, prm, (int) d.la.size(), d.ra, d.a.data(), wa.data());
-                d.gb = g2g_group_create(ctx, prm, (int) d.lb.size(), d.rb, d.b.data(), wb.data());
+                const bool hwa = side_weights(R, ga, w, wa), hwb = side_weights(R, gb, w, wb);
+                d.ga = g2g_group_create(ctx, prm, (int) d.la.size(), d.ra, d.a.data(), hwa ? wa.data() : 0);
+                d.gb = g2g_group_create(ctx, prm, (int) d.lb.size(), d.rb, d.b.data(), hwb ? wb.data() : 0);
                 if (d.ga && d.gb) d.pw = g2g_pwdm_create(ctx, prm, d.ga, d.gb, &d.swp);
                 if (!d.pw) { d.status = G2G_ERR_ARG; d.err = g2g_last_error(); continue; }      // (this thread's error string: kept for the caller's thread)
                 if (d.swp) { Skl t; swap_skl(d.old, t); d.old.swap(t); }
@@ -352,7 +403,7 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
         }
         t_build += now() - t0;
         for (int k = 0; k < nw && local_rc == G2G_OK; ++k)
-            if (D[k].status) { local_rc = D[k].status; local_err = "g2g_refine: building a division's groups failed: " + D[k].err; }
+            if (D[k].status) { local_rc = D[k].status; local_err = W + ": building a division's groups failed: " + D[k].err; }
         // ---- score: my share of the window (largest rectangles first, round-robin), then the exchange ----
         std::vector<int> live;
         for (int k = 0; k < nw; ++k) if (!D[k].skip) live.push_back(k);
@@ -378,10 +429,10 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
                 const double t1 = now();
                 rc = O.scorer(O.scorer_user, nm, pw.data(), cur.data(), ncur.data(), scr.data(), skl.data(), nskl.data(), raw.data(), val.data());
                 t_align += now() - t1;
-                if (rc != G2G_OK) g2g_set_error("%s", "g2g_refine: the scorer callback failed");
+                if (rc != G2G_OK) g2g_set_error("%s: the scorer callback failed", who);
                 for (int i = 0; i < nm && rc == G2G_OK; ++i) {
                     Division &d = D[live[mine[i]]];
-                    if (!skl[i] || nskl[i] < 2) { rc = G2G_ERR_DEVICE; g2g_set_error("%s", "g2g_refine: the scorer callback returned no skeleton"); break; }
+                    if (!skl[i] || nskl[i] < 2) { rc = G2G_ERR_DEVICE; g2g_set_error("%s: the scorer callback returned no skeleton", who); break; }
                     d.scr = scr[i]; d.val_old = raw[i]; d.val_new = val[i];
                     d.neu.assign(skl[i], skl[i] + nskl[i]);
                 }
@@ -406,7 +457,7 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
                     Division &d = D[live[mine[i]]];
                     if (st[i] != 0 || fc[i].status != 0 || fn[i].status != 0) {
                         rc = st[i] ? st[i] : fc[i].status ? fc[i].status : fn[i].status;
-                        g2g_set_error("%s", "g2g_refine: a division's DP or its sum-of-pairs score failed");
+                        g2g_set_error("%s: a division's DP or its sum-of-pairs score failed", who);
                         break;
                     }
                     d.scr = scr[i]; d.val_old = fc[i].raw; d.val_new = fn[i].val;
@@ -428,7 +479,7 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
             for (int i = 0; i < nm && local_rc == G2G_OK; ++i) {
                 const Division &d = D[live[mine[i]]];
                 int32_t *s = &mybuf[2 + (size_t) i * slot_ints];
-                if ((int) d.neu.size() > O.slot_cap) { local_rc = G2G_ERR_ARG; local_err = "g2g_refine: a skeleton exceeds the exchange slot capacity"; break; }
+                if ((int) d.neu.size() > O.slot_cap) { local_rc = G2G_ERR_ARG; local_err = W + ": a skeleton exceeds the exchange slot capacity"; break; }
                 s[0] = mine[i]; s[1] = 0; s[2] = (int32_t) d.neu.size();
                 memcpy(s + 3, &d.scr, 8); memcpy(s + 5, &d.val_old, 8); memcpy(s + 7, &d.val_new, 8);
                 for (size_t k = 0; k < d.neu.size(); ++k) { s[9 + 2 * k] = d.neu[k].m; s[10 + 2 * k] = d.neu[k].n; }
@@ -437,14 +488,14 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
             if (local_rc != G2G_OK) for (size_t q = 2; q < mybuf.size(); ++q) mybuf[q] = -1;       // a failed rank hands over no slot
             const int xrc = O.exchange(O.exchange_user, mybuf.data(), rank_ints, all.data());
             if (xrc != 0) {       // (the callback is the caller's collective: when it fails it must fail on every rank)
-                g2g_set_error("%s", "g2g_refine: the exchange callback failed"); rc_all = G2G_ERR_DEVICE;
+                g2g_set_error("%s: the exchange callback failed", who); rc_all = G2G_ERR_DEVICE;
             } else {
                 for (int r = 0; r < O.world && rc_all == G2G_OK; ++r) {
                     const int32_t st_r = all[(size_t) r * rank_ints];
                     if (st_r == G2G_OK) continue;
                     rc_all = st_r < 0 ? st_r : G2G_ERR_DEVICE;
                     if (r == O.rank && !local_err.empty()) g2g_set_error("%s", local_err.c_str());
-                    else { char who[96]; snprintf(who, sizeof who, "g2g_refine: rank %d failed (its code is this call's return value)", r); g2g_set_error("%s", who); }
+                    else { rf_err("%s: rank %d failed (its code is this call's return value)", who, r); }
                 }
             }
             int seen = 0;
@@ -455,7 +506,7 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
                     if (s[0] < 0) continue;                                                     // an unused slot
                     // slot contents crossed a process boundary: nothing in them is trusted
                     if (s[0] >= ntot || got[s[0]] || s[2] < 2 || s[2] > O.slot_cap) {
-                        g2g_set_error("%s", "g2g_refine: the exchange returned a malformed slot"); rc_all = G2G_ERR_DEVICE; break;
+                        g2g_set_error("%s: the exchange returned a malformed slot", who); rc_all = G2G_ERR_DEVICE; break;
                     }
                     got[s[0]] = 1;
                     Division &d = D[live[s[0]]];
@@ -464,7 +515,7 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
                     for (int k = 0; k < s[2]; ++k) { d.neu[k].m = s[9 + 2 * k]; d.neu[k].n = s[10 + 2 * k]; }
                     ++seen;
                 }
-            if (rc_all == G2G_OK && seen != ntot) { g2g_set_error("%s", "g2g_refine: the exchange did not return every division of the window"); rc_all = G2G_ERR_DEVICE; }
+            if (rc_all == G2G_OK && seen != ntot) { g2g_set_error("%s: the exchange did not return every division of the window", who); rc_all = G2G_ERR_DEVICE; }
         } else if (local_rc != G2G_OK) {
             g2g_set_error("%s", local_err.c_str());
             rc_all = local_rc;
@@ -488,7 +539,7 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
             ++consumed; ++it;
             g2g_refine_step e;
             memset(&e, 0, sizeof e);
-            e.t_ms = t_window;
+            e.t_ms = t_base + t_window;
             e.branch = d.branch; e.na = (int) d.la.size(); e.nb = (int) d.lb.size();
             if (d.skip) {
                 e.skipped = 1; e.delta = -INFINITY;
@@ -502,10 +553,10 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
             log.push_back(e);
             if (ok) {
                 Msa N;
-                if (!join_columns(d, d.neu_ab, many, N)) { g2g_set_error("%s", "g2g_refine: a skeleton does not describe an alignment of its two groups"); rc_all = G2G_ERR_DEVICE; break; }
+                if (!join_columns(d, d.neu_ab, many, N)) { g2g_set_error("%s: a skeleton does not describe an alignment of its two groups", who); rc_all = G2G_ERR_DEVICE; break; }
                 M.len = N.len; M.c.swap(N.c);
                 if (O.on_accept) O.on_accept(O.on_accept_user, d.branch, (int) d.la.size(), d.la.data(), (int) d.lb.size(), d.lb.data(), (int) d.neu_ab.size(), d.neu_ab.data());
-                nrep = 1; accepted = true; ++S.accepted;
+                nrep = 1; accepted = true; ++S.accepted; ++res.accepted; res.gain += d.delta;
                 break;
             }
             ++nrep;
@@ -520,12 +571,16 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
     if (rc_all != G2G_OK) return rc_all;
     t_rest = now() - t_begin - t_build - t_align;
     if (getenv("G2G_REFINE_TIMES")) fprintf(stderr, "[g2g_refine] %d batches: build %.0f ms, scoring (align2 + calcSpScore, or the scorer callback) %.0f ms, rest %.0f ms\n", S.batches, t_build, t_align, t_rest);
-    S.divisions = (int) log.size();
-    if (ctx) {        // waits of the DP scheduler that ran into their limit during this call, and the DPs re-run for it (0 in an ordinary run)
-        long long cnt1[4] = {0, 0, 0, 0};
-        g2g_ctx_counters(ctx, cnt1);
-        S.wait_timeouts = (int) (cnt1[1] - cnt0[1]); S.recovered_dps = (int) (cnt1[2] - cnt0[2]);
-    }
+    // rir leaves its loop by `break` with the loop variable at the last division's index, or by running out of iterations with it
+    // one further: countaln is the one or the other
+    const int done = (int) (log.size() - log0);
+    res.countaln = nrep >= cycle ? done - 1 : done;
+    return G2G_OK;
+}
+
+// the results of either entry point, handed out malloc'ed
+int hand_out(const Msa &M, const std::vector<g2g_refine_step> &log, uint8_t **out_codes, int *out_len, g2g_refine_step **steps, int *nsteps)
+{
     *out_len = M.len;
     *out_codes = (uint8_t *) malloc(M.c.size() ? M.c.size() : 1);
     if (!*out_codes) return G2G_ERR_NOMEM;
@@ -536,6 +591,204 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
         if (!*steps) { free(*out_codes); *out_codes = 0; return G2G_ERR_NOMEM; }
         memcpy(*steps, log.data(), sizeof(g2g_refine_step) * log.size());
     }
+    return G2G_OK;
+}
+
+// waits of the DP scheduler that ran into their limit during a call, and the DPs re-run for it (0 in an ordinary run)
+void note_counters(g2g_ctx *ctx, const long long cnt0[4], g2g_refine_stats &S)
+{
+    if (!ctx) return;
+    long long cnt1[4] = {0, 0, 0, 0};
+    g2g_ctx_counters(ctx, cnt1);
+    S.wait_timeouts = (int) (cnt1[1] - cnt0[1]); S.recovered_dps = (int) (cnt1[2] - cnt0[2]);
+}
+
+// a subset as the plan carries it: num groups that partition the members 0 .. many - 1, none empty
+const char *check_subset(const g2g_subset *ss, int many)
+{
+    if (ss->num < 1 || ss->elms != many || !ss->start || !ss->member) return "the subset must hold every member once";
+    if (ss->start[0] != 0 || ss->start[ss->num] != many) return "the subset's starts must run from 0 to the member count";
+    for (int g = 0; g < ss->num; ++g) if (ss->start[g + 1] <= ss->start[g]) return "a group of the subset is empty or the starts descend";
+    std::vector<char> seen((size_t) many, 0);
+    for (int i = 0; i < many; ++i) {
+        const int m = ss->member[i];
+        if (m < 0 || m >= many) return "a member of the subset is out of range";
+        if (seen[(size_t) m]) return "a member stands in the subset twice";
+        seen[(size_t) m] = 1;
+    }
+    return 0;
+}
+
+// a relation of the plan: its subset, its tree over the groups (as check_tree checks a tree), its origin inside n_origin nodes
+const char *check_relation(const g2g_relation *r, int many, int n_origin)
+{
+    if (const char *why = check_subset(&r->ss, many)) return why;
+    if (r->n_nodes != 2 * r->ss.num - 1) return "the tree must have 2 * num - 1 nodes";
+    if (!r->left || !r->right || !r->parent || !r->vol || !r->cur) return "the tree's arrays are missing";
+    g2g_tree t;
+    t.n_nodes = r->n_nodes; t.left = r->left; t.right = r->right; t.parent = r->parent; t.vol = r->vol; t.cur = r->cur;
+    if (const char *why = check_tree(&t, r->ss.num)) return why;
+    if (r->origin) for (int k = 0; k < r->n_nodes; ++k) if (r->origin[k] < 0 || r->origin[k] >= n_origin) return "an origin is out of range";
+    return 0;
+}
+
+}   // namespace
+
+extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len, const uint8_t *codes, const g2g_tree *tree,
+                          const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len, g2g_refine_step **steps, int *nsteps,
+                          g2g_refine_stats *stats)
+{
+    if (!prm || !codes || !tree || !out_codes || !out_len || many < 2 || len < 1) return G2G_ERR_ARG;
+    if (!ctx && !(opts && opts->scorer)) return G2G_ERR_ARG;               // the DPs run on the GPU unless the caller scores them
+    if (tree->n_nodes != 2 * many - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
+        g2g_set_error("%s", "g2g_refine: the tree must have 2 * many - 1 nodes (leaves 0 .. many - 1 = the members)");
+        return G2G_ERR_ARG;
+    }
+    if (const char *why = check_tree(tree, many)) { g2g_set_error("g2g_refine: malformed tree: %s", why); return G2G_ERR_ARG; }
+    g2g_refine_opts O;
+    if (int rc = fill_opts(opts, O, "g2g_refine")) return rc;
+
+    Rel R;
+    R.T.nn = tree->n_nodes; R.T.nleaf = many; R.T.left = tree->left; R.T.right = tree->right; R.T.parent = tree->parent; R.T.vol = tree->vol; R.T.cur = tree->cur;
+    R.group.resize((size_t) many);
+    for (int m = 0; m < many; ++m) R.group[(size_t) m].assign(1, m);
+    R.weight = 0;
+    Msa M;
+    M.len = len; M.many = many; M.c.assign(codes, codes + (size_t) len * many);
+    std::vector<g2g_refine_step> log;
+    g2g_refine_stats S;
+    memset(&S, 0, sizeof S);
+    long long cnt0[4] = {0, 0, 0, 0};
+    if (ctx) g2g_ctx_counters(ctx, cnt0);
+    GlibcRand libc;
+    LoopResult res;
+    if (int rc = refine_loop(ctx, prm, O, R, libc, M, log, S, res, 0., "g2g_refine")) return rc;
+    S.divisions = (int) log.size();
+    note_counters(ctx, cnt0, S);
+    if (int rc = hand_out(M, log, out_codes, out_len, steps, nsteps)) return rc;
     if (stats) *stats = S;
     return G2G_OK;
 }
+
+// IterMsa::preprrn's loop over the attack ranges (src/prrn5.cc:806-818): one Prrn per range, from the last range to the first,
+// on the columns of the range and over the range's own relation; all of them on one rand() state
+extern "C" int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                                  const double *weight, const g2g_tree *tree, const g2g_refine_plan_t *plan,
+                                  const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len,
+                                  g2g_refine_step **steps, int *nsteps, g2g_refine_range_stat **rstat, int *nrstat,
+                                  g2g_refine_stats *stats)
+{
+    const char *who = "g2g_refine_planned";
+    if (!prm || !codes || !tree || !out_codes || !out_len || many < 2 || len < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if ((rstat == 0) != (nrstat == 0)) { g2g_set_error("%s: rstat and nrstat go together", who); return G2G_ERR_ARG; }
+    if (!ctx && !(plan && opts && opts->scorer)) {
+        g2g_set_error("%s: without a context the caller gives the plan and scores the DPs", who);
+        return G2G_ERR_ARG;
+    }
+    // what the plan refuses (g2g_refine_plan): with tgapf = 1 the exgl / exgr switch of prrn5.cc:814-815 changes nothing the DP reads
+    if (prm->banded != 1) { g2g_set_error("%s: banded must be 1", who); return G2G_ERR_MODE; }
+    if (prm->u0 > 0) { g2g_set_error("%s: ether scorers (u0 > 0) are not on this path", who); return G2G_ERR_MODE; }
+    if ((float) prm->tgapf != 1.f) { g2g_set_error("%s: the terminal-gap discount is not on this path", who); return G2G_ERR_MODE; }
+    if (tree->n_nodes != 2 * many - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
+        g2g_set_error("%s: the tree must have 2 * many - 1 nodes (leaves 0 .. many - 1 = the members)", who);
+        return G2G_ERR_ARG;
+    }
+    if (const char *why = check_tree(tree, many)) { rf_err("%s: malformed tree: %s", who, why); return G2G_ERR_ARG; }
+    g2g_refine_opts O;
+    if (int rc = fill_opts(opts, O, who)) return rc;
+
+    g2g_refine_plan_t own;
+    memset(&own, 0, sizeof own);
+    struct Release { g2g_refine_plan_t *p; ~Release() { if (p) g2g_refine_plan_free(p); } } release = {0};
+    if (!plan) {
+        if (int rc = g2g_refine_plan(ctx, prm, thr, many, len, codes, weight, tree, &own)) return rc;
+        release.p = &own;
+        plan = &own;
+    }
+    const bool nothing = plan->status == G2G_PLAN_NOTHING_TO_REFINE;
+    const int nr = nothing ? 0 : plan->nranges;
+    if (plan->status != G2G_PLAN_OK && !nothing) { g2g_set_error("%s: a plan's status is 0 or G2G_PLAN_NOTHING_TO_REFINE", who); return G2G_ERR_ARG; }
+    if (nr < 0 || (nr > 0 && (!plan->ranges || !plan->range_rel))) { g2g_set_error("%s: the plan's ranges are missing", who); return G2G_ERR_ARG; }
+    if (nr > 0) {
+        if (const char *why = check_relation(&plan->whole, many, tree->n_nodes)) { rf_err("%s: malformed plan (the whole-MSA relation): %s", who, why); return G2G_ERR_ARG; }
+    }
+    for (int r = 0; r < nr; ++r) {
+        const g2g_range &g = plan->ranges[r];
+        if (g.left < 0 || g.right > len || g.left >= g.right || (r > 0 && g.left < plan->ranges[r - 1].right)) {
+            rf_err("%s: malformed plan: range %d [%d, %d) is empty, leaves the %d columns or does not lie behind range %d", who, r, g.left, g.right, len, r - 1);
+            return G2G_ERR_ARG;
+        }
+        if (const char *why = check_relation(&plan->range_rel[r], many, plan->whole.n_nodes)) { rf_err("%s: malformed plan (the relation of range %d): %s", who, r, why); return G2G_ERR_ARG; }
+    }
+    // a leaf group without a residue inside its range: what the reference does with the empty mSeq is not restated
+    for (int r = 0; r < nr; ++r) {
+        const g2g_relation &rel = plan->range_rel[r];
+        if (rel.ss.num < 2) continue;
+        for (int g = 0; g < rel.ss.num; ++g) {
+            bool any = false;
+            for (int c = plan->ranges[r].left; c < plan->ranges[r].right && !any; ++c)
+                for (int i = rel.ss.start[g]; i < rel.ss.start[g + 1] && !any; ++i) any = codes[(size_t) c * many + rel.ss.member[i]] != GAP;
+            if (!any) {
+                rf_err("%s: group %d of range %d [%d, %d) has no residue inside the range", who, g, r, plan->ranges[r].left, plan->ranges[r].right);
+                return G2G_ERR_MODE;
+            }
+        }
+    }
+
+    Msa M;
+    M.len = len; M.many = many; M.c.assign(codes, codes + (size_t) len * many);
+    std::vector<g2g_refine_step> log;
+    std::vector<g2g_refine_range_stat> RS((size_t) nr);
+    g2g_refine_stats S;
+    memset(&S, 0, sizeof S);
+    long long cnt0[4] = {0, 0, 0, 0};
+    if (ctx) g2g_ctx_counters(ctx, cnt0);
+    GlibcRand libc;
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int r = nr - 1; r >= 0; --r) {
+        const g2g_relation &rel = plan->range_rel[r];
+        const int left = plan->ranges[r].left, right = plan->ranges[r].right, num = rel.ss.num;
+        g2g_refine_range_stat &rs = RS[(size_t) r];
+        memset(&rs, 0, sizeof rs);
+        rs.range = r; rs.left = left; rs.right = right; rs.groups = num; rs.cycle = num >= 2 ? 2 * num - 3 : 0;
+        rs.first_step = (int32_t) log.size();
+        rs.out_left = left; rs.out_right = right;
+        rs.at_left = plan->at_left ? plan->at_left[r] : left == 0;
+        rs.at_right = plan->at_right ? plan->at_right[r] : right == len;
+        if (num < 2) continue;                                                       // Prrn::Prrn, num <= 1: nothing is drawn
+        Rel R;
+        R.T.nn = rel.n_nodes; R.T.nleaf = num; R.T.left = rel.left; R.T.right = rel.right; R.T.parent = rel.parent; R.T.vol = rel.vol; R.T.cur = rel.cur;
+        R.group.resize((size_t) num);
+        for (int g = 0; g < num; ++g) R.group[(size_t) g].assign(rel.ss.member + rel.ss.start[g], rel.ss.member + rel.ss.start[g + 1]);
+        R.weight = weight;
+        // the ranges still to come lie to the left: the columns [left, right) of the current MSA are the input's
+        Msa sub;
+        sub.many = many; sub.len = right - left;
+        sub.c.assign(M.c.begin() + (size_t) left * many, M.c.begin() + (size_t) right * many);
+        LoopResult res;
+        const double t_base = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        if (int rc = refine_loop(ctx, prm, O, R, libc, sub, log, S, res, t_base, who)) return rc;
+        std::vector<uint8_t> joined;
+        joined.reserve(M.c.size() + sub.c.size());
+        joined.insert(joined.end(), M.c.begin(), M.c.begin() + (size_t) left * many);
+        joined.insert(joined.end(), sub.c.begin(), sub.c.end());
+        joined.insert(joined.end(), M.c.begin() + (size_t) right * many, M.c.end());
+        M.c.swap(joined);
+        M.len += sub.len - (right - left);
+        rs.nsteps = (int32_t) log.size() - rs.first_step;
+        rs.divisions = res.countaln; rs.accepted = res.accepted; rs.gain = res.gain;
+        rs.out_right = left + sub.len;
+    }
+    S.divisions = (int) log.size();
+    note_counters(ctx, cnt0, S);
+    if (int rc = hand_out(M, log, out_codes, out_len, steps, nsteps)) return rc;
+    if (rstat) {
+        *nrstat = nr;
+        *rstat = (g2g_refine_range_stat *) malloc(sizeof(g2g_refine_range_stat) * (size_t) (nr ? nr : 1));
+        if (!*rstat) { free(*out_codes); *out_codes = 0; if (steps && nsteps) { free(*steps); *steps = 0; } return G2G_ERR_NOMEM; }
+        memcpy(*rstat, RS.data(), sizeof(g2g_refine_range_stat) * (size_t) nr);
+    }
+    if (stats) *stats = S;
+    return G2G_OK;
+}
+

@@ -412,6 +412,39 @@ def _take_relation(r: "_abi.Relation") -> Relation:
                     i32(r.parent, nn), i32(r.origin, nn), f64(r.vol, nn), f64(r.cur, nn))
 
 
+def _relation_struct(rel: Relation):
+    """(g2g_relation over numpy arrays, the arrays to keep alive): a Relation on its way back into the library"""
+    s, keep_s = _subset_struct(rel.groups)
+    arrs = [np.ascontiguousarray(a, np.int32) for a in (rel.left, rel.right, rel.parent, rel.origin)]
+    vc = [np.ascontiguousarray(a, np.float64) for a in (rel.vol, rel.cur)]
+    r = _abi.Relation()
+    r.fused, r.ss, r.n_nodes = int(bool(rel.fused)), s, len(arrs[0])
+    r.left, r.right, r.parent, r.origin = (a.ctypes.data_as(_abi.c_i32p) for a in arrs)
+    r.vol, r.cur = (a.ctypes.data_as(_abi.c_f64p) for a in vc)
+    return r, (keep_s, arrs, vc)
+
+
+def plan_struct(plan: RefinePlan):
+    """(g2g_refine_plan_t over numpy arrays, the arrays to keep alive) of what refine_plan returned, or of a plan made by hand.
+    Nothing in it belongs to the library: it is not to be handed to g2g_refine_plan_free."""
+    n = len(plan.ranges)
+    if len(plan.relations) != n:
+        raise ValueError("one relation per range")
+    p = _abi.RefinePlan()
+    p.status, p.nranges = (1 if plan.nothing_to_refine else 0), n
+    p.whole, keep_w = _relation_struct(plan.whole)
+    rng = (_abi.Range * max(1, n))(*[_abi.Range(int(l), int(r)) for l, r in np.asarray(plan.ranges, np.int32).reshape(-1, 2)])
+    al, ar = (np.ascontiguousarray(a, np.int32) for a in (plan.at_left, plan.at_right))
+    if len(al) != n or len(ar) != n:
+        raise ValueError("at_left / at_right: one entry per range")
+    rels = [_relation_struct(r) for r in plan.relations]
+    rr = (_abi.Relation * max(1, n))(*[r for r, _ in rels])
+    p.ranges, p.range_rel = C.cast(rng, C.POINTER(_abi.Range)), C.cast(rr, C.POINTER(_abi.Relation))
+    p.at_left, p.at_right = al.ctypes.data_as(_abi.c_i32p), ar.ctypes.data_as(_abi.c_i32p)
+    p.stats = _abi.FuseStats(plan.stats.tests, plan.stats.fused, plan.stats.launches, 0)
+    return p, (keep_w, rng, al, ar, rels, rr)
+
+
 def may_fuse_batch(ctx, pwds: Sequence, u: float = 3., v: float = 10.) -> Tuple[np.ndarray, np.ndarray]:
     """g2g_mayfuse_batch <-> ConservedT::mayfuse (reference src/consreg.cc:452-464) on built pairs (operator.PwdM) whose two groups
     are juxtaposed sons of one MSA: (fuse int32[n] 0 / 1, stop_col int32[n]: the column at which the walk broke, -1 when fused).

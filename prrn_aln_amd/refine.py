@@ -107,43 +107,86 @@ def torch_exchange(device=None):
     return _abi.EXCHANGE_FN(cb), rank, world
 
 
-def refine_native(ctx, codes: np.ndarray, tree: KTree, alp: op.AlnParam, seed: int = 1, maxitr: int = 10, window: int = 32,
-                  exchange=None, scorer=None, window_min: int = 0, want_moves: bool = False, slot_cap: int = 0):
-    """g2g_refine: (refined MSA (len, many) uint8, [step dicts], stats dict).  `exchange`: the triple torch_exchange returns, for
-    a run sharded over ranks.  `scorer`: an _abi.SCORE_FN standing in for the GPU (tests; ctx may then be None).  With
-    want_moves every accepted move is recorded as stats["moves"] = [(branch, la, lb, skl (n, 2))]."""
-    L = lib()
-    codes = np.ascontiguousarray(codes, np.uint8)
-    ln, many = codes.shape
-    prm, _sm = alp.to_c()
-    T, _keep = tree.to_c()
+def _refine_opts(seed: int = 1, maxitr: int = 10, window: int = 32, exchange=None, scorer=None, window_min: int = 0,
+                 want_moves: bool = False, slot_cap: int = 0):
+    """(g2g_refine_opts, the accepted moves' list or None, objects to keep alive)"""
     O = _abi.RefineOpts()
     O.seed, O.maxitr, O.window, O.window_min, O.slot_cap = seed, maxitr, window, window_min, slot_cap
     if exchange is not None:
         O.exchange, O.rank, O.world = exchange
     if scorer is not None:
         O.scorer = scorer
-    moves = []
+    moves, acb = None, None
     if want_moves:
+        moves = []
+
         def on_accept(user, branch, na, la, nb, lb, nskl, skl):
             moves.append((branch, [la[i] for i in range(na)], [lb[i] for i in range(nb)],
                           np.array([(skl[i].m, skl[i].n) for i in range(nskl)], np.int32).reshape(-1, 2)))
         acb = _abi.ACCEPT_FN(on_accept)
         O.on_accept = acb
-    out = _abi.c_u8p(); olen = C.c_int(); steps = C.POINTER(_abi.RefineStep)(); ns = C.c_int(); st = _abi.RefineStats()
-    rc = L.g2g_refine(ctx._h if ctx is not None else None, C.byref(prm), many, ln, codes.ctypes.data_as(_abi.c_u8p), C.byref(T), C.byref(O),
-                      C.byref(out), C.byref(olen), C.byref(steps), C.byref(ns), C.byref(st))
-    if rc != 0:
-        raise G2GError("g2g_refine rc=%d: %s" % (rc, last_error()))
+    return O, moves, acb
+
+
+def _take_results(many, out, olen, steps, ns, st, moves):
+    """(final MSA, step dicts, stats dict) out of the library's arrays, which are released"""
+    L = lib()
     final = np.ctypeslib.as_array(out, shape=(olen.value * many,)).reshape(olen.value, many).copy()
     L.g2g_free(out)
     log = [dict(branch=s.branch, na=s.na, nb=s.nb, swp=bool(s.swp), accepted=bool(s.accepted), skipped=bool(s.skipped), scr=s.scr,
                 val_new=s.val_new, val_old=s.val_old, delta=s.delta, t_ms=s.t_ms) for s in (steps[i] for i in range(ns.value))]
     L.g2g_free(steps)
     stats = {k: getattr(st, k) for k, _ in _abi.RefineStats._fields_ if k != "reserved"}
-    if want_moves:
+    if moves is not None:
         stats["moves"] = moves
     return final, log, stats
+
+
+def refine_native(ctx, codes: np.ndarray, tree: KTree, alp: op.AlnParam, seed: int = 1, maxitr: int = 10, window: int = 32,
+                  exchange=None, scorer=None, window_min: int = 0, want_moves: bool = False, slot_cap: int = 0):
+    """g2g_refine: (refined MSA (len, many) uint8, [step dicts], stats dict).  `exchange`: the triple torch_exchange returns, for
+    a run sharded over ranks.  `scorer`: an _abi.SCORE_FN standing in for the GPU (tests; ctx may then be None).  With
+    want_moves every accepted move is recorded as stats["moves"] = [(branch, la, lb, skl (n, 2))]."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    ln, many = codes.shape
+    prm, _sm = alp.to_c()
+    T, _keep = tree.to_c()
+    O, moves, _acb = _refine_opts(seed, maxitr, window, exchange, scorer, window_min, want_moves, slot_cap)
+    out = _abi.c_u8p(); olen = C.c_int(); steps = C.POINTER(_abi.RefineStep)(); ns = C.c_int(); st = _abi.RefineStats()
+    rc = lib().g2g_refine(ctx._h if ctx is not None else None, C.byref(prm), many, ln, codes.ctypes.data_as(_abi.c_u8p), C.byref(T), C.byref(O),
+                          C.byref(out), C.byref(olen), C.byref(steps), C.byref(ns), C.byref(st))
+    if rc != 0:
+        raise G2GError("g2g_refine rc=%d: %s" % (rc, last_error()))
+    return _take_results(many, out, olen, steps, ns, st, moves)
+
+
+def refine_planned(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None, plan=None, plan_prm=None, **opts):
+    """g2g_refine_planned: prrn's default refinement -- fused groups move as blocks, only the unconserved column ranges are refined,
+    from the last to the first.  prm: the parameters of the DPs (the alignment's).  plan: what guide.refine_plan returned (or a
+    guide.RefinePlan made by hand).  plan None: with plan_prm the plan is made here first by guide.refine_plan(ctx, ..., plan_prm,
+    thr, weight) -- the reference decides it with parameters of its own (its localprm and similarity matrix number 1), not the
+    alignment's; without plan_prm the library makes it with prm itself.  Either way a context is needed.  weight as for
+    guide.refine_plan; opts as for refine_native.  Returns (refined MSA (len, many) uint8, [step dicts] of the ranges in processing
+    order, [range dicts] in the plan's order, stats dict)."""
+    from . import guide
+    if plan is None and plan_prm is not None:
+        plan = guide.refine_plan(ctx, codes, tree, plan_prm, thr, weight)
+    codes, w = guide._msa_args(codes, weight)
+    ln, many = codes.shape
+    T, _keep = guide._tree_struct(tree)
+    P, _keep_p = guide.plan_struct(plan) if plan is not None else (None, None)
+    O, moves, _acb = _refine_opts(**opts)
+    out = _abi.c_u8p(); olen = C.c_int(); steps = C.POINTER(_abi.RefineStep)(); ns = C.c_int(); st = _abi.RefineStats()
+    rs = C.POINTER(_abi.RefineRangeStat)(); nrs = C.c_int()
+    rc = lib().g2g_refine_planned(ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
+                                  None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(T), None if P is None else C.byref(P),
+                                  C.byref(O), C.byref(out), C.byref(olen), C.byref(steps), C.byref(ns), C.byref(rs), C.byref(nrs), C.byref(st))
+    if rc != 0:
+        raise G2GError("g2g_refine_planned rc=%d: %s" % (rc, last_error()))
+    ranges = [{k: getattr(rs[i], k) for k, _ in _abi.RefineRangeStat._fields_ if k != "reserved"} for i in range(nrs.value)]
+    lib().g2g_free(rs)
+    final, log, stats = _take_results(many, out, olen, steps, ns, st, moves)
+    return final, log, ranges, stats
 
 
 def pairsum(ctx, codes: np.ndarray, tree: KTree, alp: op.AlnParam, use_pw: bool = True) -> float:
