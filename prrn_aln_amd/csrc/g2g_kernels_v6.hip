@@ -404,14 +404,27 @@ __device__ __forceinline__ bool v6_cell_pf(const DevProb &P, const LS6 &W, const
         double g0 = 0, g1 = 0, g2 = 0, g3 = 0;
         bool l0 = true, l1 = do_vert, l2 = do_vert, l3 = do_vert && NOLL3;
         for (int d = 0; d < DL_GUARD; ++d) {
+            // a merge is over at its list's end: decided BEFORE the wave's exit test, so that the iteration behind the wave's longest
+            // list -- ring reads, lookups and the whole select chain for sums that no lane keeps -- is not run to find that out
+#ifdef V6_NO_YTAIL                                          // (diagnostic build: the list ends are found inside the iteration)
             if (wave_none(l0 || l1 || l2 || l3)) break;
+#else
+            {
+                l0 = l0 && d < B.lent;
+                const bool lv = d < B.lenr;
+                l1 = l1 && lv; l2 = l2 && lv; l3 = l3 && lv;
+                if (wave_none(l0 || l1 || l2 || l3)) break;
+            }
+#endif
             const int dr = d - (B.lenr > B.lent ? 1 : 0);                          // entry d of the r view: the head, or t entry d - 1 / d
             const SE6 et = se6_read(B.rt, B.ot + d), ert = se6_read(B.rt, B.ot + (dr < 0 ? 0 : dr));
             SE6 er;
             er.key = dr < 0 ? 0xFFFFu : ert.key + 0x10000u; er.f = dr < 0 ? B.rhf : ert.f; er.g = (int) (er.key >> 16);
+#ifdef V6_NO_YTAIL
             l0 = l0 && d < B.lent;
             const bool lv = d < B.lenr;
             l1 = l1 && lv; l2 = l2 && lv; l3 = l3 && lv;
+#endif
             const unsigned j0 = dh_stretch<NE, SCAN>(et.key, b_hd, W, W.ib), j1 = dh_stretch<NE, SCAN>(er.key, b_gu, W, W.ib), j2 = dh_stretch<NE, SCAN>(er.key, b_hu, W, W.ib);
             const unsigned j3 = NOLL3 ? dh_stretch<NE, SCAN>(er.key, b_g2, W, W.ib) : 0u;
             l0 = l0 && m_hd >= j0; l1 = l1 && m_gu >= j1; l2 = l2 && m_hu >= j2; l3 = l3 && m_g2 >= j3;       // cf exhausted: break
@@ -526,6 +539,14 @@ __device__ __forceinline__ bool v6_cell_pf(const DevProb &P, const LS6 &W, const
         ND6 n_f = {0, 0, 0, do_hori}, n_h = {0, 0, 0, win == 0}, n_f2 = {0, 0, 0, do_hori && NOLL3};
         lu32 *const f_d2 = win == 3 ? dh + ca4 : nul, *const f2_d2 = win == 4 ? dh + ca4 : nul;
         for (int k = 0; k < DL_GUARD; ++k) {
+#ifndef V6_NO_BTAIL                                         // (diagnostic build without it: a newdelta goes off inside the step behind its list)
+            // the step at the list's end stores nothing and keeps kd, tn, tg (emit is false for g < 0): all it does is to drop .on,
+            // which is done here, in front of the wave's exit test -- the wave leaves without that step's ring read, lookups and sink stores
+            {
+                const bool in = k < B.lent;
+                n_f.on = n_f.on && in; n_h.on = n_h.on && in; n_f2.on = n_f2.on && in;
+            }
+#endif
             if (wave_none(n_f.on || n_h.on || (NOLL3 && n_f2.on))) break;
             const SE6 e = se6_read(B.rt, B.ot + k);
             const int g = k < B.lent ? e.g : -1;
