@@ -1,4 +1,4 @@
-"""ctypes mirror of include/g2g.h (the C ABI of libg2g.so).  Plumbing only."""
+"""ctypes mirror of include/g2g.h and include/g2g_progressive.h (the C ABI of libg2g.so).  Plumbing only."""
 from __future__ import annotations
 
 import ctypes as C
@@ -147,6 +147,26 @@ class RefineStep(C.Structure):
 class RefineStats(C.Structure):
     _fields_ = [("divisions", C.c_int32), ("accepted", C.c_int32), ("batches", C.c_int32), ("divisions_scored_here", C.c_int32),
                 ("divisions_wasted", C.c_int32), ("wait_timeouts", C.c_int32), ("recovered_dps", C.c_int32), ("reserved", C.c_int32)]
+
+
+ALIGN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_double), C.POINTER(C.POINTER(Skl)), C.POINTER(C.c_int),
+                       C.POINTER(C.c_int))
+
+
+class ProgOpts(C.Structure):
+    """g2g_prog_opts (include/g2g_progressive.h)"""
+    _fields_ = [("max_batch", C.c_int32), ("reserved", C.c_int32), ("aligner", ALIGN_FN), ("aligner_user", C.c_void_p)]
+
+
+class ProgMerge(C.Structure):
+    """g2g_prog_merge: one inner node of g2g_progressive"""
+    _fields_ = [("node", C.c_int32), ("left", C.c_int32), ("right", C.c_int32), ("na", C.c_int32), ("nb", C.c_int32), ("swp", C.c_int32),
+                ("mode", C.c_int32), ("wave", C.c_int32), ("len", C.c_int32), ("reserved", C.c_int32), ("scr", C.c_double), ("t_ms", C.c_double)]
+
+
+class ProgStats(C.Structure):
+    _fields_ = [("merges", C.c_int32), ("waves", C.c_int32), ("largest_wave", C.c_int32), ("wait_timeouts", C.c_int32),
+                ("recovered_dps", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RefineRangeStat(C.Structure):

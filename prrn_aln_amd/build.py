@@ -26,7 +26,7 @@ UNITS = {
     "v6": ("g2g_tu_v6.hip", [_K1, _K2, _K3, "g2g_kernels_v6.hip"]),
     "v78": ("g2g_tu_v78.hip", [_K1, _K2, _K3, "g2g_kernels_v6.hip", "g2g_kernels_v7.hip", "g2g_kernels_v8.hip"]),
     "host": ("g2g_host.cpp", ["g2g_group.h"]),
-    "refine": ("g2g_refine.cpp", []),
+    "refine": ("g2g_refine.cpp", ["../../include/g2g_progressive.h"]),      # (host only: g2g_refine and g2g_progressive)
 }
 
 # -ffp-contract=off: device AND host doubles must never be fused into FMAs (bit-exact parity with the

@@ -30,6 +30,7 @@
 #include <atomic>
 #include <chrono>
 #include "../../include/g2g.h"
+#include "../../include/g2g_progressive.h"
 #include "g2g_internal.h"
 
 extern "C" void g2g_ctx_counters(const g2g_ctx *c, long long out[4]);
@@ -792,3 +793,197 @@ extern "C" int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double th
     return G2G_OK;
 }
 
+
+// ---- the progressive alignment over a guide tree (include/g2g_progressive.h) -----------------------------------------------------
+// <-> ProgMsa::prog_up (reference src/prrn5.h:85-105).  The reference recurses post-order, one align2 at a time; a merge reads
+// nothing but its two sons, so every node whose sons are done can be merged at once: the tree is walked in waves, the DPs of a wave
+// are one batch.  A finished node is a block of columns ([column][member], an Msa) and the input indices of its members.
+namespace {
+
+struct ProgNode {
+    Msa blk;
+    std::vector<int32_t> order;
+    g2g_group *grp;
+    bool done;
+    ProgNode() : grp(0), done(false) {}
+};
+
+// the guide tree as prog_up walks it: vol / cur are not read.  0 when sound, else the node at fault in *bad
+const char *check_guide_tree(const g2g_tree *t, int nseq, int *bad)
+{
+    const int nn = t->n_nodes;
+    int root = -1;
+    for (int k = 0; k < nn; ++k) {                              // every node by itself ...
+        *bad = k;
+        const int l = t->left[k], r = t->right[k], p = t->parent[k];
+        if (l < -1 || l >= nn || r < -1 || r >= nn || p < -1 || p >= nn) return "an index is out of range";
+        if (k < nseq) { if (l != -1 || r != -1) return "a leaf (nodes 0 .. nseq - 1) has sons"; }
+        else if (l < 0 || r < 0) return "an inner node needs two sons";
+        else if (l == r || l == k || r == k) return "an inner node needs two different sons, neither of them itself";
+    }
+    for (int k = 0; k < nn; ++k) {                              // ... then the links between them
+        *bad = k;
+        const int l = t->left[k], r = t->right[k], p = t->parent[k];
+        if (p < 0) { if (root >= 0) return "a second root (there must be exactly one)"; root = k; }
+        else if (t->left[p] != k && t->right[p] != k) return "the node is not a son of its parent";
+        if (l >= 0 && t->parent[l] != k) { *bad = l; return "the node's parent is not the father that names it as its left son"; }
+        if (r >= 0 && t->parent[r] != k) { *bad = r; return "the node's parent is not the father that names it as its right son"; }
+    }
+    *bad = -1;
+    if (root < 0) return "no root";
+    std::vector<char> seen((size_t) nn, 0);
+    std::vector<int> st(1, root);
+    int cnt = 0;
+    while (!st.empty()) {
+        const int k = st.back(); st.pop_back();
+        if (seen[(size_t) k]) { *bad = k; return "the node is reached twice"; }
+        seen[(size_t) k] = 1; ++cnt;
+        if (t->left[k] >= 0) { st.push_back(t->left[k]); st.push_back(t->right[k]); }
+    }
+    if (cnt != nn) {
+        for (int k = 0; k < nn; ++k) if (!seen[(size_t) k]) { *bad = k; break; }
+        return "the node does not hang below the root";
+    }
+    return 0;
+}
+
+}   // namespace
+
+extern "C" int g2g_progressive(g2g_ctx *ctx, const g2g_params *prm, int nseq, const g2g_dseq *seqs, const g2g_tree *tree,
+                               const g2g_prog_opts *opts, uint8_t **out_codes, int *out_len, int32_t *order,
+                               g2g_prog_merge **merges, int *nmerges, g2g_prog_stats *stats)
+{
+    const char *who = "g2g_progressive";
+    if (!prm || !seqs || !tree || !out_codes || !out_len || !order || nseq < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if ((merges == 0) != (nmerges == 0)) { g2g_set_error("%s: merges and nmerges go together", who); return G2G_ERR_ARG; }
+    g2g_prog_opts O;
+    memset(&O, 0, sizeof O);
+    if (opts) O = *opts;
+    if (O.reserved != 0 || O.max_batch < 0) { g2g_set_error("%s: max_batch >= 0 and reserved = 0", who); return G2G_ERR_ARG; }
+    // 64 merges at a time unless told otherwise: twice g2g_refine's widest window, and a batch of that many DPs of the size a
+    // progressive alignment meets (two blocks of at most a few thousand columns) fits the engine's arena in one piece
+    if (O.max_batch == 0) O.max_batch = 64;
+    if (!ctx && !O.aligner) { g2g_set_error("%s: the DPs run on the GPU unless the caller aligns them: a context is needed", who); return G2G_ERR_ARG; }
+    if (prm->banded != 1) { g2g_set_error("%s: banded must be 1", who); return G2G_ERR_MODE; }
+    if (prm->u0 > 0) { g2g_set_error("%s: ether scorers (u0 > 0) are not on this path", who); return G2G_ERR_MODE; }
+    if ((float) prm->tgapf != 1.f) { g2g_set_error("%s: the terminal-gap discount is not on this path", who); return G2G_ERR_MODE; }
+    for (int i = 0; i < nseq; ++i)
+        if (!seqs[i].res || seqs[i].len < 1 || seqs[i].left != 0 || seqs[i].right != seqs[i].len) {
+            rf_err("%s: sequence %d must be given whole (left = 0, right = len >= 1)", who, i);
+            return G2G_ERR_ARG;
+        }
+    if (tree->n_nodes != 2 * nseq - 1 || !tree->left || !tree->right || !tree->parent) {
+        g2g_set_error("%s: the tree must have 2 * nseq - 1 nodes (leaves 0 .. nseq - 1 = the sequences)", who);
+        return G2G_ERR_ARG;
+    }
+    int bad = -1;
+    if (const char *why = check_guide_tree(tree, nseq, &bad)) { rf_err("%s: malformed tree at node %d: %s", who, bad, why); return G2G_ERR_ARG; }
+
+    const int nn = tree->n_nodes;
+    std::vector<ProgNode> N((size_t) nn);
+    for (int i = 0; i < nseq; ++i) {
+        ProgNode &v = N[(size_t) i];
+        v.blk.many = 1; v.blk.len = seqs[i].len; v.blk.c.assign(seqs[i].res, seqs[i].res + seqs[i].len);
+        v.order.assign(1, i);
+        v.done = true;
+    }
+    std::vector<g2g_prog_merge> log;
+    g2g_prog_stats S;
+    memset(&S, 0, sizeof S);
+    long long cnt0[4] = {0, 0, 0, 0};
+    if (ctx) g2g_ctx_counters(ctx, cnt0);
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = now();
+    auto release = [&](int k) { ProgNode &v = N[(size_t) k]; if (v.grp) g2g_group_free(v.grp); v.grp = 0; std::vector<uint8_t>().swap(v.blk.c); };
+
+    int rc = G2G_OK, left_to_merge = nn - nseq;
+    std::vector<char> merged((size_t) nn, 0);
+    while (left_to_merge > 0 && rc == G2G_OK) {
+        // the wave: the nodes whose two sons are done, ascending, at most max_batch of them
+        std::vector<int> wave;
+        for (int k = nseq; k < nn && (int) wave.size() < O.max_batch; ++k)
+            if (!merged[(size_t) k] && N[(size_t) tree->left[k]].done && N[(size_t) tree->right[k]].done) wave.push_back(k);
+        const int nw = (int) wave.size();                       // (a sound tree always has one: its lowest unmerged node)
+        std::vector<g2g_group *> ga((size_t) nw), gb((size_t) nw);
+        std::vector<g2g_pwdm *> pw((size_t) nw, (g2g_pwdm *) 0);
+        std::vector<int> swp((size_t) nw, 0), nskl((size_t) nw, 0), st((size_t) nw, 0);
+        std::vector<double> scr((size_t) nw, 0.);
+        std::vector<g2g_skl *> skl((size_t) nw, (g2g_skl *) 0);
+        for (int i = 0; i < nw && rc == G2G_OK; ++i)
+            for (int son : {tree->left[wave[i]], tree->right[wave[i]]}) {
+                ProgNode &v = N[(size_t) son];
+                v.grp = g2g_group_create(ctx, prm, v.blk.many, v.blk.len, v.blk.c.data(), 0);
+                if (!v.grp) { rc = G2G_ERR_ARG; break; }
+            }
+        for (int i = 0; i < nw; ++i) { ga[i] = N[(size_t) tree->left[wave[i]]].grp; gb[i] = N[(size_t) tree->right[wave[i]]].grp; }
+        if (rc == G2G_OK) {
+            if (ctx) rc = g2g_pwdm_create_batch(ctx, prm, nw, ga.data(), gb.data(), swp.data(), pw.data());
+            else for (int i = 0; i < nw && rc == G2G_OK; ++i) { pw[i] = g2g_pwdm_create(ctx, prm, ga[i], gb[i], &swp[i]); if (!pw[i]) rc = G2G_ERR_ARG; }
+        }
+        if (rc == G2G_OK) {
+            if (O.aligner) {
+                rc = O.aligner(O.aligner_user, nw, pw.data(), scr.data(), skl.data(), nskl.data(), st.data());
+                if (rc != G2G_OK) rf_err("%s: the aligner callback failed in wave %d", who, S.waves);
+            } else rc = g2g_align2_batch(ctx, nw, pw.data(), scr.data(), skl.data(), nskl.data(), st.data());
+            ++S.waves;
+            if (nw > S.largest_wave) S.largest_wave = nw;
+        }
+        for (int i = 0; i < nw && rc == G2G_OK; ++i)
+            if (st[i] != 0) { rc = st[i]; rf_err("%s: the DP of node %d came back with status %d", who, wave[i], st[i]); }
+        const double t_wave = now() - t_begin;
+        for (int i = 0; i < nw && rc == G2G_OK; ++i) {
+            const int k = wave[i];
+            // syntheseq on the swapped order: the PwdM's a side first
+            ProgNode &A = N[(size_t) (swp[i] ? tree->right[k] : tree->left[k])], &B = N[(size_t) (swp[i] ? tree->left[k] : tree->right[k])];
+            const int na = A.blk.many, nb = B.blk.many;
+            Division d;
+            d.la.resize((size_t) na); d.lb.resize((size_t) nb);
+            for (int m = 0; m < na; ++m) d.la[m] = m;
+            for (int m = 0; m < nb; ++m) d.lb[m] = na + m;
+            d.a.swap(A.blk.c); d.b.swap(B.blk.c);
+            d.ra = A.blk.len; d.rb = B.blk.len;
+            ProgNode &v = N[(size_t) k];
+            if (!skl[i] || !join_columns(d, Skl(skl[i], skl[i] + nskl[i]), na + nb, v.blk)) {
+                rf_err("%s: the skeleton of node %d does not describe an alignment of its two sons", who, k);
+                rc = G2G_ERR_DEVICE;
+                break;
+            }
+            v.order = A.order;
+            v.order.insert(v.order.end(), B.order.begin(), B.order.end());
+            v.done = true;
+            const g2g_problem *q = g2g_pwdm_problem(pw[i]);
+            g2g_prog_merge e;
+            memset(&e, 0, sizeof e);
+            e.node = k; e.left = tree->left[k]; e.right = tree->right[k]; e.na = q->a.many; e.nb = q->b.many; e.swp = swp[i];
+            e.mode = q->alnmode; e.wave = S.waves - 1; e.len = v.blk.len; e.scr = scr[i]; e.t_ms = t_wave;
+            log.push_back(e);
+            merged[(size_t) k] = 1;
+            --left_to_merge;
+        }
+        for (int i = 0; i < nw; ++i) {
+            g2g_free(skl[i]);
+            if (pw[i]) g2g_pwdm_free(pw[i]);
+            release(tree->left[wave[i]]); release(tree->right[wave[i]]);
+        }
+    }
+    if (rc != G2G_OK) return rc;                                // (every group and PwdM went with its wave; the blocks go with N)
+
+    int root = 0;
+    for (int k = 0; k < nn; ++k) if (tree->parent[k] < 0) root = k;
+    const ProgNode &R = N[(size_t) root];
+    S.merges = (int32_t) log.size();
+    if (ctx) {
+        long long cnt1[4] = {0, 0, 0, 0};
+        g2g_ctx_counters(ctx, cnt1);
+        S.wait_timeouts = (int) (cnt1[1] - cnt0[1]); S.recovered_dps = (int) (cnt1[2] - cnt0[2]);
+    }
+    uint8_t *oc = (uint8_t *) malloc(R.blk.c.size() ? R.blk.c.size() : 1);
+    g2g_prog_merge *om = merges ? (g2g_prog_merge *) malloc(sizeof(g2g_prog_merge) * (log.size() ? log.size() : 1)) : 0;
+    if (!oc || (merges && !om)) { free(oc); free(om); return G2G_ERR_NOMEM; }
+    memcpy(oc, R.blk.c.data(), R.blk.c.size());
+    *out_codes = oc; *out_len = R.blk.len;
+    for (int m = 0; m < nseq; ++m) order[m] = R.order[(size_t) m];
+    if (merges) { memcpy(om, log.data(), sizeof(g2g_prog_merge) * log.size()); *merges = om; *nmerges = (int) log.size(); }
+    if (stats) *stats = S;
+    return G2G_OK;
+}

@@ -7,8 +7,8 @@ sequences of a family, as the reference's dpscore() computes them (src/phyl.cc:2
 
 All DPs of the N (N - 1) / 2 pairs go to the device as ONE batch (g2g_alnscored_batch: the sequences are uploaded once, a
 pair is two indices).  For families too large for one DP per pair, kmer_distance gives the reference's k-mer composition
-distance (calcdist_kmer, src/qdiv.cc:245-282) in the same layout.  There is no CPU fallback: without libg2g.so / a GPU the
-calls raise."""
+distance (calcdist_kmer, src/qdiv.cc:245-282) in the same layout.  progressive / align_sequences (at the end) take the guide tree
+of either to the first MSA.  There is no CPU fallback: without libg2g.so / a GPU the calls raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -516,3 +516,60 @@ def refine_plan(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 3
                       [_take_relation(out.range_rel[i]) for i in range(n)], FuseStats(out.stats.tests, out.stats.fused, out.stats.launches))
     lib().g2g_refine_plan_free(C.byref(out))
     return plan
+
+
+# ---- the progressive alignment over a guide tree (the step between the guide tree and the first MSA) -------------------------------
+def progressive(ctx, seqs: Sequence[np.ndarray], tree, prm: "_abi.Params", max_batch: int = 0, aligner=None):
+    """g2g_progressive <-> ProgMsa::prog_up (reference src/prrn5.h:85-105): the sequences (arrays of residue codes, taken whole) are
+    merged up the guide tree -- leaves 0 .. n - 1 = the sequences; a refine.KTree, e.g. KTree.from_dist(dist, with_weights=False), or
+    anything with left, right, parent -- in waves of independent merges, at most max_batch (0: the library's default, 64) DPs to a
+    batch.  aligner: an _abi.ALIGN_FN standing in for g2g_align2_batch (tests; ctx may then be None).
+    Returns (codes (len, n) uint8 with gap = 1, order int32[n]: the input index of every member, [merge dicts] in the order merged,
+    stats dict)."""
+    L = lib()
+    n = len(seqs)
+    ds = (_abi.DSeq * max(n, 1))()
+    keep = []
+    for k, s in enumerate(seqs):
+        x = np.ascontiguousarray(s, np.uint8).reshape(-1)
+        keep.append(x)
+        ds[k].res = x.ctypes.data_as(_abi.c_u8p)
+        ds[k].len, ds[k].left, ds[k].right = len(x), 0, len(x)
+    T, _keep_t = _tree_struct(tree)
+    O = _abi.ProgOpts()
+    O.max_batch = int(max_batch)
+    if aligner is not None:
+        O.aligner = aligner
+    out = _abi.c_u8p(); olen = C.c_int(); order = np.zeros(max(n, 1), np.int32)
+    mg = C.POINTER(_abi.ProgMerge)(); nm = C.c_int(); st = _abi.ProgStats()
+    rc = L.g2g_progressive(ctx._h if ctx is not None else None, C.byref(prm), n, ds, C.byref(T), C.byref(O), C.byref(out), C.byref(olen),
+                           order.ctypes.data_as(_abi.c_i32p), C.byref(mg), C.byref(nm), C.byref(st))
+    if rc != 0:
+        raise G2GError("g2g_progressive rc=%d: %s" % (rc, last_error()))
+    codes = np.ctypeslib.as_array(out, shape=(olen.value * n,)).reshape(olen.value, n).copy()
+    L.g2g_free(out)
+    merges = [{k: getattr(mg[i], k) for k, _ in _abi.ProgMerge._fields_ if k != "reserved"} for i in range(nm.value)]
+    L.g2g_free(mg)
+    stats = {k: getattr(st, k) for k, _ in _abi.ProgStats._fields_ if k != "reserved"}
+    return codes, order[:n].copy(), merges, stats
+
+
+def align_sequences(ctx, seqs: Sequence[np.ndarray], molc: int, alp, distance: str = "kmer", input_order: bool = True):
+    """Unaligned sequences -> the start MSA, as makemsa chains it (reference src/prrn5.cc:961-995): the distances -- "kmer":
+    kmer_distance with the reference's defaults, "dp": distance_matrix with the alignment's parameters --, the guide tree
+    KTree.from_dist(dist, with_weights=False), and progressive.  alp: an operator.AlnParam.  Returns (codes (len, n) uint8, tree,
+    order): with input_order the columns of codes are permuted back so that member k is sequence k (order is then 0 .. n - 1), else
+    member k is sequence order[k].  Refinement stays a separate call: KTree.from_msa + refine.refine_planned."""
+    from .refine import KTree
+    if distance not in ("kmer", "dp"):
+        raise ValueError('distance is "kmer" or "dp"')
+    prm, sm = alp.to_c()
+    dist = kmer_distance(ctx, seqs, molc) if distance == "kmer" else distance_matrix(ctx, prm, seqs, sm)
+    tree = KTree.from_dist(dist, with_weights=False)
+    codes, order, _merges, _stats = progressive(ctx, seqs, tree, prm)
+    if input_order:
+        back = np.empty_like(order)
+        back[order] = np.arange(len(order), dtype=order.dtype)
+        codes = np.ascontiguousarray(codes[:, back])
+        order = np.arange(len(order), dtype=np.int32)
+    return codes, tree, order
