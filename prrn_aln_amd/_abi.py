@@ -259,3 +259,16 @@ class SpParams(C.Structure):
 class Fstat(C.Structure):
     _fields_ = [("val", C.c_double), ("gap", C.c_double), ("status", C.c_int32), ("reserved", C.c_int32), ("raw", C.c_double),
                 ("mch", C.c_double), ("mmc", C.c_double), ("unp", C.c_double)]
+
+
+def bind_groups(L) -> None:
+    """argument types of include/g2g_groups.h: the weighting tree over groups the caller brings"""
+    i32p = C.POINTER(C.c_int32)
+    L.g2g_msa_divergence_groups.argtypes = [C.c_void_p, C.c_int, C.c_int, c_u8p, C.POINTER(Subset), c_f64p, i32p]
+    L.g2g_ktree_from_dist_leaves.argtypes = [C.c_int, c_f64p, i32p, c_f64p, c_f64p, C.c_int, C.POINTER(KTreeOut)]
+    L.g2g_ktree_from_msa_groups.argtypes = [C.c_void_p, C.c_int, C.c_int, c_u8p, C.POINTER(Subset), C.c_int, C.POINTER(KTreeOut), c_f64p, c_f64p]
+    head = [C.c_void_p, C.POINTER(Params), C.c_double, C.c_int, C.c_int, c_u8p, c_f64p, C.POINTER(Tree), C.POINTER(Subset)]
+    L.g2g_refine_plan_groups.argtypes = head + [C.POINTER(RefinePlan)]
+    L.g2g_refine_planned_groups.argtypes = head + [C.POINTER(RefinePlan), C.POINTER(RefineOpts), C.POINTER(c_u8p), C.POINTER(C.c_int),
+                                                   C.POINTER(C.POINTER(RefineStep)), C.POINTER(C.c_int), C.POINTER(C.POINTER(RefineRangeStat)),
+                                                   C.POINTER(C.c_int), C.POINTER(RefineStats)]

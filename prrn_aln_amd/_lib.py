@@ -118,6 +118,7 @@ def lib():
     L.g2g_progressive.argtypes = [C.c_void_p, C.POINTER(_abi.Params), C.c_int, C.POINTER(_abi.DSeq), C.POINTER(_abi.Tree), C.POINTER(_abi.ProgOpts),
                                   C.POINTER(_abi.c_u8p), C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.POINTER(_abi.ProgMerge)),
                                   C.POINTER(C.c_int), C.POINTER(_abi.ProgStats)]
+    _abi.bind_groups(L)
     bind_level1(L)
     _lib = L
     return L

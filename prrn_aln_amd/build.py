@@ -20,13 +20,13 @@ HDR = [os.path.join(os.path.dirname(HERE), "include", "g2g.h"), os.path.join(CSR
 _K1, _K2, _K3 = "g2g_kernels.hip", "g2g_kernels_v2.hip", "g2g_kernels_v3.hip"
 # unit -> (source, files it includes besides the headers)
 UNITS = {
-    "engine": ("g2g_engine.hip", [_K1, _K2, _K3, "g2g_kernels_v6.hip", "g2g_kernels_v7.hip", "g2g_kernels_v8.hip", "g2g_dist.hip", "g2g_pairaln.hip", "g2g_pairsum.hip", "g2g_ktree.hip", "g2g_kmer.hip", "g2g_consreg.hip", "g2g_build.hip", "g2g_group.h", "g2g_plan.h"]),
+    "engine": ("g2g_engine.hip", [_K1, _K2, _K3, "g2g_kernels_v6.hip", "g2g_kernels_v7.hip", "g2g_kernels_v8.hip", "g2g_dist.hip", "g2g_pairaln.hip", "g2g_pairsum.hip", "g2g_ktree.hip", "g2g_ktree_groups.hip", "../../include/g2g_groups.h", "g2g_kmer.hip", "g2g_consreg.hip", "g2g_build.hip", "g2g_group.h", "g2g_plan.h"]),
     "v2": ("g2g_tu_v2.hip", [_K1, _K2]),
     "v3": ("g2g_tu_v3.hip", [_K1, _K2, _K3]),
     "v6": ("g2g_tu_v6.hip", [_K1, _K2, _K3, "g2g_kernels_v6.hip"]),
     "v78": ("g2g_tu_v78.hip", [_K1, _K2, _K3, "g2g_kernels_v6.hip", "g2g_kernels_v7.hip", "g2g_kernels_v8.hip"]),
     "host": ("g2g_host.cpp", ["g2g_group.h"]),
-    "refine": ("g2g_refine.cpp", ["../../include/g2g_progressive.h"]),      # (host only: g2g_refine and g2g_progressive)
+    "refine": ("g2g_refine.cpp", ["../../include/g2g_progressive.h", "../../include/g2g_groups.h"]),      # (host only: g2g_refine, g2g_progressive, g2g_refine_planned_groups)
 }
 
 # -ffp-contract=off: device AND host doubles must never be fused into FMAs (bit-exact parity with the

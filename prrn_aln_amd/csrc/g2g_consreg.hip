@@ -867,24 +867,25 @@ extern "C" void g2g_refine_plan_free(g2g_refine_plan_t *p)
 }
 
 // what IterMsa::preprrn decides before any Prrn is built (prrn5.cc:794-823)
-extern "C" int g2g_refine_plan(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,
-                               const g2g_tree *tree, g2g_refine_plan_t *out)
+// -- from singletons (groups NULL), or from a relation the caller brings: tree is then the tree over `groups`
+static int cr_refine_plan(const char *who, g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,
+                          const g2g_tree *tree, const g2g_subset *groups, g2g_refine_plan_t *out)
 {
-    const char *who = "g2g_refine_plan";
     if (!prm || !codes || !tree || !out || len < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
     memset(out, 0, sizeof *out);
     if (many < 2) { g2g_set_error("%s: fewer than two members", who); return G2G_ERR_ARG; }
     if (!(thr > 0)) { g2g_set_error("%s: thr must be positive", who); return G2G_ERR_ARG; }
     int rc = cr_mode_check(prm, who);
     if (rc != G2G_OK) return rc;
-    if (const char *bad = cr_check_relation(tree, many, 0, many, 0)) { cr_err(who, "%s", bad); return G2G_ERR_ARG; }
+    const int nl = groups ? groups->num : many;
+    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { cr_err(who, "%s", bad); return G2G_ERR_ARG; }
     if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
     if (!ctx->ok) return G2G_ERR_NODEVICE;
     const bool timed = g2g_opt(ctx, "FUSE_TIMING") != 0;
     if (timed) ctx->opt.erase("FUSE_KERNEL_MS");
     CrBuildTimes tm;
     CrRel rel0, srl;
-    cr_rel_from(rel0, tree, many, 0);
+    cr_rel_from(rel0, tree, nl, groups);
     {   // rrl = consregss(infc); srl = rrl ? rrl : this
         std::vector<CrFuseJob> jobs(1);
         jobs[0].rel = &rel0; jobs[0].left = 0; jobs[0].right = len;
@@ -924,6 +925,20 @@ extern "C" int g2g_refine_plan(g2g_ctx *ctx, const g2g_params *prm, double thr, 
     if (rc != G2G_OK) { g2g_refine_plan_free(out); return rc; }
     if (timed) cr_fuse_note(ctx, tm);
     return G2G_OK;
+}
+
+extern "C" int g2g_refine_plan(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,
+                               const g2g_tree *tree, g2g_refine_plan_t *out)
+{
+    return cr_refine_plan("g2g_refine_plan", ctx, prm, thr, many, len, codes, weight, tree, NULL, out);
+}
+
+// include/g2g_groups.h: the plan started from the caller's relation instead of singletons
+extern "C" int g2g_refine_plan_groups(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,
+                                      const g2g_tree *tree, const g2g_subset *groups, g2g_refine_plan_t *out)
+{
+    if (!groups) { g2g_set_error("%s", "g2g_refine_plan_groups: bad argument"); return G2G_ERR_ARG; }
+    return cr_refine_plan("g2g_refine_plan_groups", ctx, prm, thr, many, len, codes, weight, tree, groups, out);
 }
 
 extern "C" int g2g_consreg(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,

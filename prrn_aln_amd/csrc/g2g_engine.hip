@@ -1707,6 +1707,7 @@ extern "C" int g2g_forward_batch(g2g_ctx *ctx, int n, const g2g_problem *const *
 #include "g2g_pairaln.hip"             // f3: alignB_ng (pairwise alignment of single sequences with the path)
 #include "g2g_pairsum.hip"             // f1: Ssrel::pairsum_ss (naive nodes on the GPU, joins through calcSpScore)
 #include "g2g_ktree.hip"               // the weighting tree of an MSA: divergence kernel, UPGMA, Kirchhoff weights
+#include "g2g_ktree_groups.hip"        // the weighting tree over given groups: group divergence kernels, preset leaves, phyl_pwt
 #include "g2g_kmer.hip"                // k-mer composition distances of unaligned sequences: profile and pair kernels, closed forms
 #include "g2g_consreg.hip"             // the conserved regions of an MSA: Ssrel::constwo / consreg (column scores and the range scan)
 #include "g2g_build.hip"             // a8 / a9: thickness, vectors and gap profiles of a batch of groups on the device

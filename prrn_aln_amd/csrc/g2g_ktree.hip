@@ -133,6 +133,8 @@ inline size_t kt_elem(int i, int j) { return i < j ? (size_t) j * (j - 1) / 2 + 
 
 struct KtBuilder {
     int many;
+    const int32_t *leaf_ndesc = 0;                                    // what IterMsa::phyl_pwt puts into lead[k] before Ktree(msd, ss, UPG_METHOD, lead)
+    const double *leaf_height = 0, *leaf_res = 0;                     // (src/prrn5.cc:364-371): leaves that are sub-alignments; NULL: 1 / 0 / 0
     std::vector<double> dist;                                         // the working copy: upg_method averages in place
     std::vector<KtNode> lead;
     std::vector<int> row, nnbr, nodes;
@@ -173,7 +175,9 @@ struct KtBuilder {
         int m = 0;
         for (size_t k = 0; m < members; ++m) {
             nodes[m] = row[m] = m;
-            lead[m].ndesc = 1;
+            lead[m].ndesc = leaf_ndesc ? std::max(leaf_ndesc[m], 1) : 1;   // phyl.cc:956
+            if (leaf_height) lead[m].height = leaf_height[m];
+            if (leaf_res) lead[m].res = leaf_res[m];
             for (int n = 0; n < m; ++n, ++k) {
                 if (dist[k] < distance(m, nnbr[m])) nnbr[m] = n;
                 if (dist[k] < distance(n, nnbr[n])) nnbr[n] = m;
@@ -281,22 +285,24 @@ extern "C" void g2g_ktree_free(g2g_ktree *t)
     memset(t, 0, sizeof *t);
 }
 
-extern "C" int g2g_ktree_from_dist(int many, const double *dist, int with_weights, g2g_ktree *out)
+// the builder behind g2g_ktree_from_dist and g2g_ktree_from_dist_leaves (include/g2g_groups.h): num leaves, preset or plain
+static int kt_tree_from_dist(const char *who, int many, const double *dist, const int32_t *ndesc, const double *height, const double *res,
+                             int with_weights, g2g_ktree *out)
 {
-    if (!dist || !out || many < 2 || many > G2G_KTREE_MAX_MEMBERS) { g2g_set_error("%s", "g2g_ktree_from_dist: bad argument (2 <= many <= 4096)"); return G2G_ERR_ARG; }
     const size_t np = (size_t) many * (many - 1) / 2;
     for (int j = 1; j < many; ++j)
         for (int i = 0; i < j; ++i) {
             const double d = dist[kt_elem(i, j)];
             if (!(d >= 0)) {                                          // (NaN included: a pair of members without a common column)
-                char msg[96];
-                snprintf(msg, sizeof msg, "distance of members %d and %d is %s", i, j, d != d ? "not a number" : "negative");
-                g2g_set_error("g2g_ktree_from_dist: %s", msg);
+                char msg[128];
+                snprintf(msg, sizeof msg, "%s: distance of members %d and %d is %s", who, i, j, d != d ? "not a number" : "negative");
+                g2g_set_error("%s", msg);
                 return G2G_ERR_ARG;
             }
         }
     KtBuilder B;
     B.many = many;
+    B.leaf_ndesc = ndesc; B.leaf_height = height; B.leaf_res = res;
     B.dist.assign(dist, dist + np);
     const int root = B.upg_method();
     if (with_weights) {                                               // Ktree::calcpw, phyl.cc:813-826
@@ -321,6 +327,12 @@ extern "C" int g2g_ktree_from_dist(int many, const double *dist, int with_weight
         out->vol[k] = with_weights ? nd.vol : 0.; out->cur[k] = with_weights ? nd.cur : 0.;
     }
     return G2G_OK;
+}
+
+extern "C" int g2g_ktree_from_dist(int many, const double *dist, int with_weights, g2g_ktree *out)
+{
+    if (!dist || !out || many < 2 || many > G2G_KTREE_MAX_MEMBERS) { g2g_set_error("%s", "g2g_ktree_from_dist: bad argument (2 <= many <= 4096)"); return G2G_ERR_ARG; }
+    return kt_tree_from_dist("g2g_ktree_from_dist", many, dist, NULL, NULL, NULL, with_weights, out);
 }
 
 extern "C" int g2g_ktree_from_msa(g2g_ctx *ctx, int many, int len, const uint8_t *codes, g2g_ktree *out)

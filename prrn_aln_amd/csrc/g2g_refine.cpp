@@ -31,6 +31,7 @@
 #include <chrono>
 #include "../../include/g2g.h"
 #include "../../include/g2g_progressive.h"
+#include "../../include/g2g_groups.h"
 #include "g2g_internal.h"
 
 extern "C" void g2g_ctx_counters(const g2g_ctx *c, long long out[4]);
@@ -672,46 +673,19 @@ extern "C" int g2g_refine(g2g_ctx *ctx, const g2g_params *prm, int many, int len
 }
 
 // IterMsa::preprrn's loop over the attack ranges (src/prrn5.cc:806-818): one Prrn per range, from the last range to the first,
-// on the columns of the range and over the range's own relation; all of them on one rand() state
-extern "C" int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
-                                  const double *weight, const g2g_tree *tree, const g2g_refine_plan_t *plan,
-                                  const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len,
-                                  g2g_refine_step **steps, int *nsteps, g2g_refine_range_stat **rstat, int *nrstat,
-                                  g2g_refine_stats *stats)
+// on the columns of the range and over the range's own relation; all of them on one rand() state.  The body of g2g_refine_planned
+// and g2g_refine_planned_groups: it reads the plan's relations alone; tree_nodes: the nodes of the tree the plan was made over.
+namespace {
+int refine_planned_run(const char *who, g2g_ctx *ctx, const g2g_params *prm, int many, int len, const uint8_t *codes, const double *weight,
+                       int tree_nodes, const g2g_refine_plan_t *plan, const g2g_refine_opts &O, uint8_t **out_codes, int *out_len,
+                       g2g_refine_step **steps, int *nsteps, g2g_refine_range_stat **rstat, int *nrstat, g2g_refine_stats *stats)
 {
-    const char *who = "g2g_refine_planned";
-    if (!prm || !codes || !tree || !out_codes || !out_len || many < 2 || len < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
-    if ((rstat == 0) != (nrstat == 0)) { g2g_set_error("%s: rstat and nrstat go together", who); return G2G_ERR_ARG; }
-    if (!ctx && !(plan && opts && opts->scorer)) {
-        g2g_set_error("%s: without a context the caller gives the plan and scores the DPs", who);
-        return G2G_ERR_ARG;
-    }
-    // what the plan refuses (g2g_refine_plan): with tgapf = 1 the exgl / exgr switch of prrn5.cc:814-815 changes nothing the DP reads
-    if (prm->banded != 1) { g2g_set_error("%s: banded must be 1", who); return G2G_ERR_MODE; }
-    if (prm->u0 > 0) { g2g_set_error("%s: ether scorers (u0 > 0) are not on this path", who); return G2G_ERR_MODE; }
-    if ((float) prm->tgapf != 1.f) { g2g_set_error("%s: the terminal-gap discount is not on this path", who); return G2G_ERR_MODE; }
-    if (tree->n_nodes != 2 * many - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
-        g2g_set_error("%s: the tree must have 2 * many - 1 nodes (leaves 0 .. many - 1 = the members)", who);
-        return G2G_ERR_ARG;
-    }
-    if (const char *why = check_tree(tree, many)) { rf_err("%s: malformed tree: %s", who, why); return G2G_ERR_ARG; }
-    g2g_refine_opts O;
-    if (int rc = fill_opts(opts, O, who)) return rc;
-
-    g2g_refine_plan_t own;
-    memset(&own, 0, sizeof own);
-    struct Release { g2g_refine_plan_t *p; ~Release() { if (p) g2g_refine_plan_free(p); } } release = {0};
-    if (!plan) {
-        if (int rc = g2g_refine_plan(ctx, prm, thr, many, len, codes, weight, tree, &own)) return rc;
-        release.p = &own;
-        plan = &own;
-    }
     const bool nothing = plan->status == G2G_PLAN_NOTHING_TO_REFINE;
     const int nr = nothing ? 0 : plan->nranges;
     if (plan->status != G2G_PLAN_OK && !nothing) { g2g_set_error("%s: a plan's status is 0 or G2G_PLAN_NOTHING_TO_REFINE", who); return G2G_ERR_ARG; }
     if (nr < 0 || (nr > 0 && (!plan->ranges || !plan->range_rel))) { g2g_set_error("%s: the plan's ranges are missing", who); return G2G_ERR_ARG; }
     if (nr > 0) {
-        if (const char *why = check_relation(&plan->whole, many, tree->n_nodes)) { rf_err("%s: malformed plan (the whole-MSA relation): %s", who, why); return G2G_ERR_ARG; }
+        if (const char *why = check_relation(&plan->whole, many, tree_nodes)) { rf_err("%s: malformed plan (the whole-MSA relation): %s", who, why); return G2G_ERR_ARG; }
     }
     for (int r = 0; r < nr; ++r) {
         const g2g_range &g = plan->ranges[r];
@@ -791,6 +765,96 @@ extern "C" int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double th
     }
     if (stats) *stats = S;
     return G2G_OK;
+}
+
+// what both entries refuse before they look at their tree
+int refine_planned_args(const char *who, g2g_ctx *ctx, const g2g_params *prm, int many, int len, const uint8_t *codes, const g2g_tree *tree,
+                        const g2g_refine_plan_t *plan, const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len,
+                        g2g_refine_range_stat **rstat, int *nrstat)
+{
+    if (!prm || !codes || !tree || !out_codes || !out_len || many < 2 || len < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if ((rstat == 0) != (nrstat == 0)) { g2g_set_error("%s: rstat and nrstat go together", who); return G2G_ERR_ARG; }
+    if (!ctx && !(plan && opts && opts->scorer)) {
+        g2g_set_error("%s: without a context the caller gives the plan and scores the DPs", who);
+        return G2G_ERR_ARG;
+    }
+    // what the plan refuses (g2g_refine_plan): with tgapf = 1 the exgl / exgr switch of prrn5.cc:814-815 changes nothing the DP reads
+    if (prm->banded != 1) { g2g_set_error("%s: banded must be 1", who); return G2G_ERR_MODE; }
+    if (prm->u0 > 0) { g2g_set_error("%s: ether scorers (u0 > 0) are not on this path", who); return G2G_ERR_MODE; }
+    if ((float) prm->tgapf != 1.f) { g2g_set_error("%s: the terminal-gap discount is not on this path", who); return G2G_ERR_MODE; }
+    return G2G_OK;
+}
+}   // namespace
+
+extern "C" int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                                  const double *weight, const g2g_tree *tree, const g2g_refine_plan_t *plan,
+                                  const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len,
+                                  g2g_refine_step **steps, int *nsteps, g2g_refine_range_stat **rstat, int *nrstat,
+                                  g2g_refine_stats *stats)
+{
+    const char *who = "g2g_refine_planned";
+    if (int rc = refine_planned_args(who, ctx, prm, many, len, codes, tree, plan, opts, out_codes, out_len, rstat, nrstat)) return rc;
+    if (tree->n_nodes != 2 * many - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
+        g2g_set_error("%s: the tree must have 2 * many - 1 nodes (leaves 0 .. many - 1 = the members)", who);
+        return G2G_ERR_ARG;
+    }
+    if (const char *why = check_tree(tree, many)) { rf_err("%s: malformed tree: %s", who, why); return G2G_ERR_ARG; }
+    g2g_refine_opts O;
+    if (int rc = fill_opts(opts, O, who)) return rc;
+
+    g2g_refine_plan_t own;
+    memset(&own, 0, sizeof own);
+    struct Release { g2g_refine_plan_t *p; ~Release() { if (p) g2g_refine_plan_free(p); } } release = {0};
+    if (!plan) {
+        if (int rc = g2g_refine_plan(ctx, prm, thr, many, len, codes, weight, tree, &own)) return rc;
+        release.p = &own;
+        plan = &own;
+    }
+    return refine_planned_run(who, ctx, prm, many, len, codes, weight, tree->n_nodes, plan, O, out_codes, out_len, steps, nsteps, rstat, nrstat, stats);
+}
+
+// g2g_refine_planned over groups the caller brings (include/g2g_groups.h): the tree is the tree over `groups`
+extern "C" int g2g_refine_planned_groups(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes,
+                                         const double *weight, const g2g_tree *tree, const g2g_subset *groups, const g2g_refine_plan_t *plan,
+                                         const g2g_refine_opts *opts, uint8_t **out_codes, int *out_len,
+                                         g2g_refine_step **steps, int *nsteps, g2g_refine_range_stat **rstat, int *nrstat,
+                                         g2g_refine_stats *stats)
+{
+    const char *who = "g2g_refine_planned_groups";
+    if (int rc = refine_planned_args(who, ctx, prm, many, len, codes, tree, plan, opts, out_codes, out_len, rstat, nrstat)) return rc;
+    if (!groups) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if (const char *why = check_subset(groups, many)) { rf_err("%s: malformed groups: %s", who, why); return G2G_ERR_ARG; }
+    if (groups->num < 2) { g2g_set_error("%s: fewer than two groups", who); return G2G_ERR_ARG; }
+    if (tree->n_nodes != 2 * groups->num - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
+        g2g_set_error("%s: the tree must have 2 * num - 1 nodes (leaves 0 .. num - 1 = the groups)", who);
+        return G2G_ERR_ARG;
+    }
+    if (const char *why = check_tree(tree, groups->num)) { rf_err("%s: malformed tree: %s", who, why); return G2G_ERR_ARG; }
+    g2g_refine_opts O;
+    if (int rc = fill_opts(opts, O, who)) return rc;
+
+    g2g_refine_plan_t own;
+    memset(&own, 0, sizeof own);
+    struct Release { g2g_refine_plan_t *p; ~Release() { if (p) g2g_refine_plan_free(p); } } release = {0};
+    if (!plan) {
+        if (int rc = g2g_refine_plan_groups(ctx, prm, thr, many, len, codes, weight, tree, groups, &own)) return rc;
+        release.p = &own;
+        plan = &own;
+    }
+    // a plan from elsewhere must keep every given group whole: the groups of its ranges' relations are unions of them
+    for (int r = 0; plan->status == G2G_PLAN_OK && plan->range_rel && r < plan->nranges; ++r) {
+        const g2g_subset &ps = plan->range_rel[r].ss;
+        if (check_subset(&ps, many)) continue;                                       // (refused by the shared validation below)
+        std::vector<int> of((size_t) many, -1);
+        for (int g = 0; g < ps.num; ++g) for (int i = ps.start[g]; i < ps.start[g + 1]; ++i) of[(size_t) ps.member[i]] = g;
+        for (int g = 0; g < groups->num; ++g)
+            for (int i = groups->start[g] + 1; i < groups->start[g + 1]; ++i)
+                if (of[(size_t) groups->member[i]] != of[(size_t) groups->member[groups->start[g]]]) {
+                    rf_err("%s: the relation of range %d of the plan divides group %d", who, r, g);
+                    return G2G_ERR_ARG;
+                }
+    }
+    return refine_planned_run(who, ctx, prm, many, len, codes, weight, tree->n_nodes, plan, O, out_codes, out_len, steps, nsteps, rstat, nrstat, stats);
 }
 
 

@@ -83,6 +83,27 @@ def msa_divergence(ctx, codes: np.ndarray):
     return dist, counts
 
 
+def msa_divergence_groups(ctx, codes: np.ndarray, groups):
+    """g2g_msa_divergence_groups: the divergence of every pair of GROUPS of members of an MSA as the group form of the reference's
+    pairdvn computes it (src/divseq.cc:65-105) -- the distances the weighting tree over the groups is built from.  groups: one
+    sequence of member indices per group, together a partition of the members; the order inside a group is significant.  Returns
+    (dist float64[npairs], counts int32[npairs, 4]); group pair (k < l) is entry l (l - 1) / 2 + k."""
+    codes = np.ascontiguousarray(codes, np.uint8)
+    if codes.ndim != 2:
+        raise ValueError("codes must be (len, many)")
+    ln, many = codes.shape
+    ss, keep = _subset_struct(groups)
+    npairs = max(len(groups) * (len(groups) - 1) // 2, 0)
+    dist = np.zeros(npairs, np.float64)
+    counts = np.zeros((npairs, 4), np.int32)
+    rc = lib().g2g_msa_divergence_groups(None if ctx is None else ctx._h, many, ln, codes.ctypes.data_as(_abi.c_u8p), C.byref(ss),
+                                         dist.ctypes.data_as(_abi.c_f64p), counts.ctypes.data_as(C.POINTER(C.c_int32)))
+    del keep
+    if rc != 0:
+        raise G2GError("g2g_msa_divergence_groups rc=%d: %s" % (rc, last_error()))
+    return dist, counts
+
+
 def _kmer_params(molc: int, k: int, measure: int) -> "_abi.KmerParams":
     kp = _abi.KmerParams()
     kp.molc, kp.k, kp.measure, kp.reserved = int(molc), int(k), int(measure), 0
@@ -496,17 +517,25 @@ def conserved_regions_groups(ctx, codes: np.ndarray, tree, prm: "_abi.Params", g
     return _take_ranges(out, nout.value)
 
 
-def refine_plan(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None) -> RefinePlan:
+def refine_plan(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None, groups=None) -> RefinePlan:
     """g2g_refine_plan <-> what IterMsa::preprrn decides before it refines (reference src/prrn5.cc:794-823): the fused groups of the
-    whole MSA, the unconserved ranges over them, and every range's own groups and tree."""
+    whole MSA, the unconserved ranges over them, and every range's own groups and tree.  groups: g2g_refine_plan_groups -- the plan
+    starts from these groups instead of single members, tree is the tree over them (KTree.from_msa_groups)."""
     codes, w = _msa_args(codes, weight)
     ln, many = codes.shape
     t, keep_t = _tree_struct(tree)
     out = _abi.RefinePlan()
-    rc = lib().g2g_refine_plan(ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
-                               None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(t), C.byref(out))
-    if rc != 0:
-        raise G2GError("g2g_refine_plan rc=%d: %s" % (rc, last_error()))
+    h, wp = ctx._h if ctx is not None else None, None if w is None else w.ctypes.data_as(_abi.c_f64p)
+    if groups is None:
+        rc = lib().g2g_refine_plan(h, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p), wp, C.byref(t), C.byref(out))
+        if rc != 0:
+            raise G2GError("g2g_refine_plan rc=%d: %s" % (rc, last_error()))
+    else:
+        ss, keep_s = _subset_struct(groups)
+        rc = lib().g2g_refine_plan_groups(h, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p), wp, C.byref(t), C.byref(ss),
+                                          C.byref(out))
+        if rc != 0:
+            raise G2GError("g2g_refine_plan_groups rc=%d: %s" % (rc, last_error()))
     n = out.nranges
     rng = np.zeros((n, 2), np.int32)
     if n:

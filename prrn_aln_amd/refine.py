@@ -47,18 +47,52 @@ class KTree:
         return t
 
     @classmethod
-    def from_dist(cls, dist, with_weights: bool = True) -> "KTree":
+    def from_dist(cls, dist, with_weights: bool = True, leaves=None) -> "KTree":
         """g2g_ktree_from_dist: UPGMA tree (DistTree::upg_method) of a condensed distance vector -- pair (i < j) at j (j - 1) / 2 + i --
-        and, with_weights, the Kirchhoff weights (Ktree::calcpw); host only.  Without them vol / cur are zero."""
+        and, with_weights, the Kirchhoff weights (Ktree::calcpw); host only.  Without them vol / cur are zero.
+        leaves = (ndesc, height, res), each an array of one value per leaf or None: g2g_ktree_from_dist_leaves, leaves that are
+        sub-alignments (what IterMsa::phyl_pwt puts into lead[k])."""
         d = np.ascontiguousarray(dist, np.float64).reshape(-1)
         many = int(round((1 + (1 + 8 * len(d)) ** 0.5) / 2))
         if many * (many - 1) // 2 != len(d):
             raise ValueError("%d distances are not the pairs of a whole number of members" % len(d))
         T = _abi.KTreeOut()
-        rc = lib().g2g_ktree_from_dist(many, d.ctypes.data_as(_abi.c_f64p), 1 if with_weights else 0, C.byref(T))
+        if leaves is None:
+            rc = lib().g2g_ktree_from_dist(many, d.ctypes.data_as(_abi.c_f64p), 1 if with_weights else 0, C.byref(T))
+            if rc != 0:
+                raise G2GError("g2g_ktree_from_dist rc=%d: %s" % (rc, last_error()))
+            return cls._take(T)
+        ndesc, height, res = leaves
+        nd = None if ndesc is None else np.ascontiguousarray(ndesc, np.int32)
+        hg = None if height is None else np.ascontiguousarray(height, np.float64)
+        rs = None if res is None else np.ascontiguousarray(res, np.float64)
+        if any(a is not None and a.shape != (many,) for a in (nd, hg, rs)):
+            raise ValueError("one ndesc / height / res per leaf")
+        ptr = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        rc = lib().g2g_ktree_from_dist_leaves(many, d.ctypes.data_as(_abi.c_f64p), ptr(nd, C.POINTER(C.c_int32)), ptr(hg, _abi.c_f64p),
+                                              ptr(rs, _abi.c_f64p), 1 if with_weights else 0, C.byref(T))
         if rc != 0:
-            raise G2GError("g2g_ktree_from_dist rc=%d: %s" % (rc, last_error()))
+            raise G2GError("g2g_ktree_from_dist_leaves rc=%d: %s" % (rc, last_error()))
         return cls._take(T)
+
+    @classmethod
+    def from_msa_groups(cls, ctx, codes: np.ndarray, groups, flat_leaves: bool = False):
+        """g2g_ktree_from_msa_groups: IterMsa::phyl_pwt over groups the caller brings -- (the weighting tree over the groups, the
+        members' weights).  The tree's leaves are the groups; it is the tree guide.fuse_groups / conserved_regions_groups take
+        with `groups`."""
+        from .guide import _subset_struct
+        codes = np.ascontiguousarray(codes, np.uint8)
+        ln, many = codes.shape
+        ss, keep = _subset_struct(groups)
+        T = _abi.KTreeOut()
+        weight = np.zeros(many, np.float64)
+        sumwt = C.c_double(0.)
+        rc = lib().g2g_ktree_from_msa_groups(None if ctx is None else ctx._h, many, ln, codes.ctypes.data_as(_abi.c_u8p), C.byref(ss),
+                                             1 if flat_leaves else 0, C.byref(T), weight.ctypes.data_as(_abi.c_f64p), C.byref(sumwt))
+        del keep
+        if rc != 0:
+            raise G2GError("g2g_ktree_from_msa_groups rc=%d: %s" % (rc, last_error()))
+        return cls._take(T), weight
 
     @classmethod
     def from_msa(cls, ctx, codes: np.ndarray) -> "KTree":
@@ -160,17 +194,18 @@ def refine_native(ctx, codes: np.ndarray, tree: KTree, alp: op.AlnParam, seed: i
     return _take_results(many, out, olen, steps, ns, st, moves)
 
 
-def refine_planned(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None, plan=None, plan_prm=None, **opts):
+def refine_planned(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float = 35., weight=None, plan=None, plan_prm=None, groups=None, **opts):
     """g2g_refine_planned: prrn's default refinement -- fused groups move as blocks, only the unconserved column ranges are refined,
     from the last to the first.  prm: the parameters of the DPs (the alignment's).  plan: what guide.refine_plan returned (or a
     guide.RefinePlan made by hand).  plan None: with plan_prm the plan is made here first by guide.refine_plan(ctx, ..., plan_prm,
     thr, weight) -- the reference decides it with parameters of its own (its localprm and similarity matrix number 1), not the
     alignment's; without plan_prm the library makes it with prm itself.  Either way a context is needed.  weight as for
-    guide.refine_plan; opts as for refine_native.  Returns (refined MSA (len, many) uint8, [step dicts] of the ranges in processing
-    order, [range dicts] in the plan's order, stats dict)."""
+    guide.refine_plan; opts as for refine_native.  groups: g2g_refine_planned_groups -- tree is the tree over these groups, which
+    are refined against each other and stay as they are inside.  Returns (refined MSA (len, many) uint8, [step dicts] of the ranges
+    in processing order, [range dicts] in the plan's order, stats dict)."""
     from . import guide
     if plan is None and plan_prm is not None:
-        plan = guide.refine_plan(ctx, codes, tree, plan_prm, thr, weight)
+        plan = guide.refine_plan(ctx, codes, tree, plan_prm, thr, weight, groups=groups)
     codes, w = guide._msa_args(codes, weight)
     ln, many = codes.shape
     T, _keep = guide._tree_struct(tree)
@@ -178,15 +213,33 @@ def refine_planned(ctx, codes: np.ndarray, tree, prm: "_abi.Params", thr: float 
     O, moves, _acb = _refine_opts(**opts)
     out = _abi.c_u8p(); olen = C.c_int(); steps = C.POINTER(_abi.RefineStep)(); ns = C.c_int(); st = _abi.RefineStats()
     rs = C.POINTER(_abi.RefineRangeStat)(); nrs = C.c_int()
-    rc = lib().g2g_refine_planned(ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
-                                  None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(T), None if P is None else C.byref(P),
-                                  C.byref(O), C.byref(out), C.byref(olen), C.byref(steps), C.byref(ns), C.byref(rs), C.byref(nrs), C.byref(st))
-    if rc != 0:
-        raise G2GError("g2g_refine_planned rc=%d: %s" % (rc, last_error()))
+    head = (ctx._h if ctx is not None else None, C.byref(prm), float(thr), many, ln, codes.ctypes.data_as(_abi.c_u8p),
+            None if w is None else w.ctypes.data_as(_abi.c_f64p), C.byref(T))
+    tail = (None if P is None else C.byref(P), C.byref(O), C.byref(out), C.byref(olen), C.byref(steps), C.byref(ns), C.byref(rs), C.byref(nrs),
+            C.byref(st))
+    if groups is None:
+        rc = lib().g2g_refine_planned(*head, *tail)
+        if rc != 0:
+            raise G2GError("g2g_refine_planned rc=%d: %s" % (rc, last_error()))
+    else:
+        ss, _keep_s = guide._subset_struct(groups)
+        rc = lib().g2g_refine_planned_groups(*head, C.byref(ss), *tail)
+        if rc != 0:
+            raise G2GError("g2g_refine_planned_groups rc=%d: %s" % (rc, last_error()))
     ranges = [{k: getattr(rs[i], k) for k, _ in _abi.RefineRangeStat._fields_ if k != "reserved"} for i in range(nrs.value)]
     lib().g2g_free(rs)
     final, log, stats = _take_results(many, out, olen, steps, ns, st, moves)
     return final, log, ranges, stats
+
+
+def refine_groups(ctx, codes: np.ndarray, groups, prm: "_abi.Params", thr: float = 35., flat_leaves: bool = False, plan_prm=None, **opts):
+    """prrn's refinement between groups that stay as they are (its multi-profile stage), in one call: the weighting tree over the
+    groups and the members' weights (KTree.from_msa_groups <-> IterMsa::phyl_pwt), the plan started from the groups
+    (g2g_refine_plan_groups) and the refinement over it (g2g_refine_planned_groups).  plan_prm / opts as for refine_planned.
+    Returns what refine_planned returns, then the tree and the weights."""
+    tree, weight = KTree.from_msa_groups(ctx, codes, groups, flat_leaves)
+    final, log, ranges, stats = refine_planned(ctx, codes, tree, prm, thr, weight, None, plan_prm, groups=groups, **opts)
+    return final, log, ranges, stats, tree, weight
 
 
 def pairsum(ctx, codes: np.ndarray, tree: KTree, alp: op.AlnParam, use_pw: bool = True) -> float:
