@@ -3,17 +3,20 @@
 // for the pair and walks the columns once: per column a group-to-group similarity plus the gap term of a diagonal step
 // (cons2_ng / _nv / _hf / _pf, consreg.cc:170-406), a thresholded running sum over the column scores gives ranges, and the
 // ranges of all divisions are intersected (cmnrng, src/css.cc:261-282).
-//   g2g_consreg_kernel: one workgroup per division, lanes across the columns of a tile of CR_T columns.
+// The column scores have one scorer on the device, cr_begin / cr_tile: one workgroup per pair of groups, lanes across the columns
+// of a tile of CR_T columns.
 //     1. members whose gap run in front of the column is read (_hf: b's, _nv: both sides'): one ballot per member and wave says
 //        which of the tile's columns hold a residue; the run length of (member, column) is the distance to the nearest set bit
 //        below the column -- in the lane's own wave, the waves in front of it, or the column carried in from earlier tiles
 //        (Seq::pregap with left = 0 followed by incrgap, src/seq.cc:1870-1883, src/mgaps.cc:431-440).
 //     2. a lane forms s of its column with the scorers of g2g_kernels.hip (sim2, crg2, newgap4) and stores it to LDS.
-//     3. lane 0 runs the reference's recurrence over the tile's scores in column order; its scalars stay in registers from tile
-//        to tile.  Ranges go to the division's slot in HBM.
+//     3. the kernel's lane 0 runs a recurrence of the reference over the tile's scores in column order; its scalars stay in
+//        registers from tile to tile.
+// The two kernels are their recurrences: g2g_consreg_kernel the thresholded running sum, whose ranges go to the division's slot in
+// HBM, g2g_mayfuse_kernel the walk of the fuse test, which may leave early.  On the host both entries check a pair with
+// cr_check_pair and reach the device through CrPairs.
 // Plain launch on the context's stream; no atomics, no waits on other workgroups.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
 
 #define CR_T 256                      /* columns per tile = threads per workgroup */
 #define CR_W (CR_T / 64)              /* waves */
@@ -62,64 +65,101 @@ __device__ double cr_newgap2(const DevProb &P, const int c, const unsigned long 
     return P.weighted_gop * g;
 }
 
+// ---- the tile scorer both kernels run ------------------------------------------------------------------------------------------
+// a kernel's static LDS: arrays each kernel declares for itself, as before there was one scorer
+struct CrShared {
+    double *sc;                                                // [CR_T]: s of the tile's columns
+    int *gl;                                                   // [CR_NV_MEM * CR_T], _nv: run lengths, [member][lane]
+    int2 *zero_delta;                                          // [2], ZeroDelta: newgap4 over it is newgap(cf, df), src/gfreq.cc:493-505
+    DevProb &P;
+};
+struct CrTiles {                                               // what a thread knows about its division once cr_begin has run
+    int len, kind, an, nm;                                     // nm: members whose gap runs are read
+    unsigned long long *mask;                                  // dynamic LDS [nm][CR_W]: the tile's columns with a residue, per member and wave
+    int *last;                                                 // dynamic LDS [nm]: column behind the member's last residue in front of the tile
+};
+
+// The descriptor into LDS (one barrier), last[] and ZeroDelta set.  The caller sets what else it keeps in LDS and places the barrier
+// that ends the prologue.
+__device__ __forceinline__ CrTiles cr_begin(const CrShared &S, unsigned char *dyn, const DevProb *prob)
+{
+    const int tid = threadIdx.x;
+    for (int i = tid; i < (int) (sizeof(DevProb) / 4); i += CR_T) ((int *) &S.P)[i] = ((const int *) prob)[i];
+    __syncthreads();
+    CrTiles T;
+    T.len = S.P.a.right; T.kind = S.P.kind; T.an = S.P.a.many;
+    T.nm = T.kind == 3 ? T.an + S.P.b.many : T.kind == 1 ? S.P.b.many : 0;
+    T.mask = (unsigned long long *) dyn;
+    T.last = (int *) (T.mask + (size_t) T.nm * CR_W);
+    for (int j = tid; j < T.nm; j += CR_T) T.last[j] = 0;
+    if (tid == 0) { S.zero_delta[0] = make_int2(0, 0); S.zero_delta[1] = make_int2(INT_MAX, 0); }
+    return T;
+}
+
+// The tile that starts at column c0: the ballots, a barrier, s of every live column into S.sc (and into colscore where it is given),
+// a barrier, last[] carried on to the next tile.  The caller's walk over S.sc[0 .. min(CR_T, len - c0)) follows, and behind it the
+// tile's third barrier.
+__device__ __forceinline__ void cr_tile(const CrShared &S, const CrTiles &T, const int c0, double *colscore)
+{
+    const DevProb &P = S.P;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len = T.len, kind = T.kind, an = T.an, nm = T.nm;
+    unsigned long long *mask = T.mask;
+    int *last = T.last;
+    DList zd; zd.p = S.zero_delta; zd.s = 1;
+    const int c = c0 + tid;
+    const bool live = c < len;
+    const int cc = live ? c : len - 1;
+    for (int j = 0; j < nm; ++j) {
+        const bool ina = kind == 3 && j < an;
+        const uint8_t r = ina ? res_at(P.a, cc)[j] : res_at(P.b, cc)[kind == 3 ? j - an : j];
+        const unsigned long long m = __ballot(live && r > 1);
+        if (lane == 0) mask[j * CR_W + wave] = m;
+    }
+    __syncthreads();
+    if (live) {
+        double s = sim2(P, c, c);
+        if (kind == 3) {
+            int *gl = S.gl;
+            for (int j = 0; j < nm; ++j) gl[j * CR_T + tid] = cr_runlen(mask, last, j, c0, c, wave, lane);
+            s = s + crg2(P, gl + tid, gl + an * CR_T + tid, CR_T, c, c, 0);
+        } else if (kind == 1) {
+            s = s + cr_newgap2(P, c, mask, last, c0, wave, lane);
+        } else if (kind == 2) {
+            s = s + newgap4(gfq_at(P.a, 0, c), zd, gfq_at(P.b, 1, c), zd) * P.basic_gop
+                  + newgap4(gfq_at(P.b, 0, c), zd, gfq_at(P.a, 1, c), zd) * P.basic_gop;
+        }
+        S.sc[tid] = s;
+        if (colscore) colscore[c] = s;
+    }
+    __syncthreads();
+    for (int j = tid; j < nm; j += CR_T)
+        for (int w = CR_W - 1; w >= 0; --w) {
+            const unsigned long long m = mask[j * CR_W + w];
+            if (m) { last[j] = c0 + w * 64 + (63 - __clzll((long long) m)) + 1; break; }
+        }
+}
+
 extern "C" __global__ void __launch_bounds__(CR_T) g2g_consreg_kernel(const DevProb *probs, const ConsregArgs *args)
 {
     extern __shared__ __align__(16) unsigned char cr_dyn[];
     __shared__ double sc[CR_T];
     __shared__ int gl[CR_NV_MEM * CR_T];
-    __shared__ int2 zero_delta[2];                             // ZeroDelta: newgap4 over it is newgap(cf, df), src/gfreq.cc:493-505
+    __shared__ int2 zero_delta[2];
     __shared__ DevProb P;
+    const CrShared S = {sc, gl, zero_delta, P};
     const ConsregArgs A = args[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < (int) (sizeof(DevProb) / 4); i += CR_T) ((int *) &P)[i] = ((const int *) &probs[blockIdx.x])[i];
-    __syncthreads();
-    const int len = P.a.right, kind = P.kind;
-    const int an = P.a.many, bn = P.b.many;
-    const int nm = kind == 3 ? an + bn : kind == 1 ? bn : 0;   // members whose gap runs are read
-    unsigned long long *mask = (unsigned long long *) cr_dyn;  // [nm][CR_W]
-    int *last = (int *) (mask + (size_t) nm * CR_W);           // [nm]: column behind the member's last residue in front of the tile
-    for (int j = tid; j < nm; j += CR_T) last[j] = 0;
-    if (tid == 0) { zero_delta[0] = make_int2(0, 0); zero_delta[1] = make_int2(INT_MAX, 0); }
-    DList zd; zd.p = zero_delta; zd.s = 1;
+    const CrTiles T = cr_begin(S, cr_dyn, &probs[blockIdx.x]);
     // the scan's scalars (consreg.cc:172-182; `sum` is only printed there)
     double scr = 0, mxv = 0;
     int rl = 0, rr = 0, nr = 0;
     __syncthreads();
-    for (int c0 = 0; c0 < len; c0 += CR_T) {
-        const int c = c0 + tid;
-        const bool live = c < len;
-        const int cc = live ? c : len - 1;
-        for (int j = 0; j < nm; ++j) {
-            const bool ina = kind == 3 && j < an;
-            const uint8_t r = ina ? res_at(P.a, cc)[j] : res_at(P.b, cc)[kind == 3 ? j - an : j];
-            const unsigned long long m = __ballot(live && r > 1);
-            if (lane == 0) mask[j * CR_W + wave] = m;
-        }
-        __syncthreads();
-        if (live) {
-            double s = sim2(P, c, c);
-            if (kind == 3) {
-                for (int j = 0; j < nm; ++j) gl[j * CR_T + tid] = cr_runlen(mask, last, j, c0, c, wave, lane);
-                s = s + crg2(P, gl + tid, gl + an * CR_T + tid, CR_T, c, c, 0);
-            } else if (kind == 1) {
-                s = s + cr_newgap2(P, c, mask, last, c0, wave, lane);
-            } else if (kind == 2) {
-                s = s + newgap4(gfq_at(P.a, 0, c), zd, gfq_at(P.b, 1, c), zd) * P.basic_gop
-                      + newgap4(gfq_at(P.b, 0, c), zd, gfq_at(P.a, 1, c), zd) * P.basic_gop;
-            }
-            sc[tid] = s;
-            if (A.colscore) A.colscore[c] = s;
-        }
-        __syncthreads();
-        for (int j = tid; j < nm; j += CR_T)
-            for (int w = CR_W - 1; w >= 0; --w) {
-                const unsigned long long m = mask[j * CR_W + w];
-                if (m) { last[j] = c0 + w * 64 + (63 - __clzll((long long) m)) + 1; break; }
-            }
-        if (tid == 0) {
-            const int n = len - c0 < CR_T ? len - c0 : CR_T;
+    for (int c0 = 0; c0 < T.len; c0 += CR_T) {
+        cr_tile(S, T, c0, A.colscore);
+        if (threadIdx.x == 0) {
+            const int n = T.len - c0 < CR_T ? T.len - c0 : CR_T;
             for (int k = 0; k < n; ++k) {
-                const double s = sc[k];
+                const double s = S.sc[k];
                 const int i = c0 + k;
                 if (scr == 0 && s > 0) rl = i;
                 scr += s;
@@ -134,7 +174,7 @@ extern "C" __global__ void __launch_bounds__(CR_T) g2g_consreg_kernel(const DevP
         }
         __syncthreads();
     }
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         if (scr >= A.vthr) { if (nr < A.cap) A.ranges[nr] = make_int2(rl, rr); ++nr; }
         *A.nranges = nr;
     }
@@ -142,8 +182,8 @@ extern "C" __global__ void __launch_bounds__(CR_T) g2g_consreg_kernel(const DevP
 
 // ConservedT::mayfuse (consreg.cc:452-464): may_fuse_ng / _nv / _hf / _pf (:211-225, 276-298, 345-364, 408-424) walk the same column
 // scores with another recurrence -- scr += s; a positive scr is set to 0; the walk breaks where scr < fthr -- and the pair fuses iff
-// the walk reaches the last column.  One workgroup per test, tiles and run lengths as above; when lane 0's walk breaks it leaves the
-// column in LDS and the whole workgroup leaves behind the tile's barrier.
+// the walk reaches the last column.  One workgroup per test over the same tiles; when lane 0's walk breaks it leaves the column in
+// LDS and the whole workgroup leaves behind the tile's barrier.
 struct MayfuseArgs {
     double fthr;                      // Conserved2::fthr (consreg.cc:73), formed on the host
     int2 *out;                        // {fuse, stop_col}
@@ -156,55 +196,19 @@ extern "C" __global__ void __launch_bounds__(CR_T) g2g_mayfuse_kernel(const DevP
     __shared__ int gl[CR_NV_MEM * CR_T];
     __shared__ int2 zero_delta[2];
     __shared__ DevProb P;
+    const CrShared S = {sc, gl, zero_delta, P};
     __shared__ int stop_at;                                    // the column at which scr < fthr first held, -1 while the walk goes on
     const MayfuseArgs A = args[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < (int) (sizeof(DevProb) / 4); i += CR_T) ((int *) &P)[i] = ((const int *) &probs[blockIdx.x])[i];
-    __syncthreads();
-    const int len = P.a.right, kind = P.kind;
-    const int an = P.a.many, bn = P.b.many;
-    const int nm = kind == 3 ? an + bn : kind == 1 ? bn : 0;
-    unsigned long long *mask = (unsigned long long *) cr_dyn;  // [nm][CR_W]
-    int *last = (int *) (mask + (size_t) nm * CR_W);           // [nm]
-    for (int j = tid; j < nm; j += CR_T) last[j] = 0;
-    if (tid == 0) { zero_delta[0] = make_int2(0, 0); zero_delta[1] = make_int2(INT_MAX, 0); stop_at = -1; }
-    DList zd; zd.p = zero_delta; zd.s = 1;
+    const CrTiles T = cr_begin(S, cr_dyn, &probs[blockIdx.x]);
+    if (threadIdx.x == 0) stop_at = -1;
     double scr = 0;
     __syncthreads();
-    for (int c0 = 0; c0 < len; c0 += CR_T) {
-        const int c = c0 + tid;
-        const bool live = c < len;
-        const int cc = live ? c : len - 1;
-        for (int j = 0; j < nm; ++j) {
-            const bool ina = kind == 3 && j < an;
-            const uint8_t r = ina ? res_at(P.a, cc)[j] : res_at(P.b, cc)[kind == 3 ? j - an : j];
-            const unsigned long long m = __ballot(live && r > 1);
-            if (lane == 0) mask[j * CR_W + wave] = m;
-        }
-        __syncthreads();
-        if (live) {
-            double s = sim2(P, c, c);
-            if (kind == 3) {
-                for (int j = 0; j < nm; ++j) gl[j * CR_T + tid] = cr_runlen(mask, last, j, c0, c, wave, lane);
-                s = s + crg2(P, gl + tid, gl + an * CR_T + tid, CR_T, c, c, 0);
-            } else if (kind == 1) {
-                s = s + cr_newgap2(P, c, mask, last, c0, wave, lane);
-            } else if (kind == 2) {
-                s = s + newgap4(gfq_at(P.a, 0, c), zd, gfq_at(P.b, 1, c), zd) * P.basic_gop
-                      + newgap4(gfq_at(P.b, 0, c), zd, gfq_at(P.a, 1, c), zd) * P.basic_gop;
-            }
-            sc[tid] = s;
-        }
-        __syncthreads();
-        for (int j = tid; j < nm; j += CR_T)
-            for (int w = CR_W - 1; w >= 0; --w) {
-                const unsigned long long m = mask[j * CR_W + w];
-                if (m) { last[j] = c0 + w * 64 + (63 - __clzll((long long) m)) + 1; break; }
-            }
-        if (tid == 0) {
-            const int n = len - c0 < CR_T ? len - c0 : CR_T;
+    for (int c0 = 0; c0 < T.len; c0 += CR_T) {
+        cr_tile(S, T, c0, 0);
+        if (threadIdx.x == 0) {
+            const int n = T.len - c0 < CR_T ? T.len - c0 : CR_T;
             for (int k = 0; k < n; ++k) {
-                scr += sc[k];
+                scr += S.sc[k];
                 if (scr > 0) scr = 0;
                 if (scr < A.fthr) { stop_at = c0 + k; break; }
             }
@@ -212,7 +216,7 @@ extern "C" __global__ void __launch_bounds__(CR_T) g2g_mayfuse_kernel(const DevP
         __syncthreads();
         if (stop_at >= 0) break;                               // read by every lane behind the barrier: the exit is uniform
     }
-    if (tid == 0) *A.out = make_int2(stop_at < 0 ? 1 : 0, stop_at);
+    if (threadIdx.x == 0) *A.out = make_int2(stop_at < 0 ? 1 : 0, stop_at);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
@@ -257,23 +261,94 @@ g2g_range *cr_hand_out(const CrRanges &r)
     if (p && !r.empty()) memcpy(p, r.data(), sizeof(g2g_range) * r.size());
     return p;
 }
-void cr_note_ms(g2g_ctx *ctx, const char *name, double ms, bool add)
-{
-    if (add) { const char *old = g2g_opt(ctx, name); if (old) ms += atof(old); }
-    char buf[32];
-    snprintf(buf, sizeof buf, "%.6f", ms);
-    ctx->opt[name] = std::make_pair(true, std::string(buf));
-}
-void cr_err(const char *who, const char *fmt, ...)                  // g2g_set_error takes one string: "<who>: <formatted text>"
-{
-    char buf[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g2g_set_error((std::string(who) + ": %s").c_str(), buf);
-}
 double cr_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// What g2g_constwo_batch and g2g_mayfuse_batch refuse in pair i, before the device is asked for anything; `what` is the reference's
+// function, whose switch the message names.  nm: the members whose gap runs the kernel reads.
+int cr_check_pair(const char *who, int i, const g2g_problem *p, const char *what, size_t *nm)
+{
+    int rc = G2G_OK;
+    if (p->alnmode < G2G_NGP_ALB || p->alnmode > G2G_NTV_ALB) { rc = G2G_ERR_MODE; g2g_errorf(who, "pair %d: mode %d is not a banded mode (%s's switch reads the banded names only)", i, p->alnmode, what); }
+    else if (p->a.npfq > 0 || p->b.npfq > 0) { rc = G2G_ERR_MODE; g2g_errorf(who, "pair %d: annotated (spliced) groups are not on this path", i); }
+    else if (p->a.nils || p->b.nils) { rc = G2G_ERR_MODE; g2g_errorf(who, "pair %d: groups with discounted terminal gaps are not on this path", i); }
+    else if (p->a.len != p->b.len || p->a.left != 0 || p->b.left != 0 || p->a.right != p->a.len || p->b.right != p->b.len) { rc = G2G_ERR_ARG; g2g_errorf(who, "pair %d: the two groups must have the same length and stand whole (%d and %d columns)", i, p->a.len, p->b.len); }
+    else if (p->alnmode == G2G_NTV_ALB && p->a.many + p->b.many > CR_NV_MEM) { rc = G2G_ERR_MODE; g2g_errorf(who, "pair %d: a naive-record pair of %d members", i, p->a.many + p->b.many); }
+    else if ((rc = check_problem(p)) != G2G_OK) g2g_errorf(who, "pair %d: not a problem of this library (status %d)", i, rc);
+    if (rc != G2G_OK) return rc;
+    const int kind = kind_of(p->alnmode);
+    *nm = kind == 3 ? (size_t) p->a.many + p->b.many : kind == 1 ? (size_t) p->b.many : 0;
+    return G2G_OK;
+}
+// the dynamic LDS of a launch whose largest pair reads nm_max members, [nm][CR_W] masks and [nm] last: refused beyond 48 KB
+bool cr_lds_bytes(const char *who, size_t nm_max, size_t *lds)
+{
+    *lds = (nm_max * (8 * CR_W + 4) + 15) & ~(size_t) 15;
+    if (*lds > 48 * 1024) { g2g_set_error("%s: a gap-free group of more than 1365 members on the _hf path", who); return false; }
+    return true;
+}
+
+// n built pairs on the device, one workgroup each.  The inputs as g2g_batch_prepare packs them (arrays a device builder left in
+// HBM are read where they lie) and nothing else: no DP state, no trace.  The block from the context's pool holds
+// [DevProb n][args n][the problems' arrays] and, from out() on, out_bytes for the kernel to write.  The caller packs, fills its
+// argument structs with addresses behind out(), uploads, launches on ctx->stream unless e is set, and fetches: `back` is then what
+// lies behind out().  The block returns to the pool when the object goes.
+struct CrPairs {
+    g2g_ctx *ctx; const char *who; int n;
+    Blob bl;                                                      // (the staging buffer goes back to the context with it)
+    std::vector<DevProb> dp;
+    std::vector<DevPatch> patches;
+    size_t arg_size = 0, o_probs = 0, o_args = 0, in_bytes = 0, out_bytes = 0;
+    char *dev = 0; size_t dev_cap = 0;
+    bool timed = false;
+    hipError_t e = hipSuccess;
+    std::vector<char> back;
+    CrPairs(g2g_ctx *c, const char *w, int n_) : ctx(c), who(w), n(n_), bl(c), dp((size_t) n_) {}
+    ~CrPairs() { pool_give(ctx, dev, dev_cap); }
+    char *out() const { return dev + in_bytes; }
+    const DevProb *probs() const { return (const DevProb *) (dev + o_probs); }
+    const void *args() const { return dev + o_args; }
+    int pack(const g2g_problem *const *prob, size_t arg_size_, size_t out_bytes_)
+    {
+        arg_size = arg_size_;
+        bl.grow(staging_estimate(ctx, n, prob) + arg_size * (size_t) n);
+        o_probs = bl.put(0, 0);
+        bl.extend(o_probs + sizeof(DevProb) * (size_t) n);
+        o_args = bl.put(0, 0);
+        bl.extend(o_args + arg_size * (size_t) n);
+        for (int i = 0; i < n; ++i) pack_problem(bl, prob[i], dp[(size_t) i], patches);
+        bl.flush();
+        if (bl.oom) { g2g_set_error("%s: host staging buffer: out of (pinned) memory", who); return G2G_ERR_NOMEM; }
+        in_bytes = (bl.size() + 255) & ~(size_t) 255;
+        out_bytes = out_bytes_;
+        dev = (char *) pool_take(ctx, in_bytes + out_bytes, &dev_cap);
+        if (!dev) { g2g_set_error("%s: out of device memory", who); (void) hipGetLastError(); return G2G_ERR_NOMEM; }
+        for (int i = 0; i < n; ++i) rebase_problem(dp[(size_t) i], dev);
+        for (const DevPatch &pt : patches) *pt.field = pt.value;
+        return G2G_OK;
+    }
+    // timing_switch: the diagnostic option that asks for device events around the kernel (tools/consreg_probe.py, tools/fuse_probe.py)
+    void upload(const void *args, const char *timing_switch)
+    {
+        memcpy(bl.data() + o_probs, dp.data(), sizeof(DevProb) * (size_t) n);
+        memcpy(bl.data() + o_args, args, arg_size * (size_t) n);
+        e = hipMemcpyAsync(dev, bl.data(), bl.size(), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        timed = g2g_opt(ctx, timing_switch) != 0;
+        if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[0], ctx->stream);
+    }
+    // everything behind the inputs comes back in one copy; ms_option: the kernel's time, summed over the calls since it was cleared
+    int fetch(const char *ms_option)
+    {
+        if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[1], ctx->stream);
+        back.resize(out_bytes);                                   // (here, not earlier: the kernel runs while the host clears these pages)
+        if (e == hipSuccess) e = hipMemcpyAsync(back.data(), out(), out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        else (void) hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && timed) e = g2g_note_events(ctx, ms_option, ctx->ev[0], ctx->ev[1], true);
+        if (e != hipSuccess) { g2g_errorf(who, "%s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
+        return G2G_OK;
+    }
+};
 }
 
 // host only, no context: cmnrng (dissim = 0: the intersection of a and b) or complerng (dissim = 1: [0, len) without a; b is not
@@ -298,111 +373,59 @@ extern "C" int g2g_constwo_batch(g2g_ctx *ctx, int n, g2g_pwdm *const *pw, doubl
     for (int i = 0; i < n; ++i) { ranges[i] = 0; nranges[i] = 0; if (colscore) colscore[i] = 0; if (status) status[i] = G2G_OK; }
     std::vector<const g2g_problem *> prob((size_t) n);
     std::vector<double> vthr((size_t) n);
-    size_t nm_max = 0, cols = 0;
+    // behind the inputs: nranges[n], then every division's slot of ranges and, where asked for, its column scores
+    std::vector<size_t> o_rng((size_t) n), o_col((size_t) n);
+    size_t nm_max = 0, lds = 0, out_bytes = (4 * (size_t) n + 255) & ~(size_t) 255;
     for (int i = 0; i < n; ++i) {
         const g2g_problem *p = pw[i] ? g2g_pwdm_problem(pw[i]) : 0;
         g2g_spparams sp;
         if (!p || g2g_pwdm_spparams(pw[i], &sp) != G2G_OK) { g2g_set_error("%s: a NULL pair", who); return G2G_ERR_ARG; }
-        int rc = G2G_OK;
-        char msg[160] = "";
-        if (p->alnmode < G2G_NGP_ALB || p->alnmode > G2G_NTV_ALB) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: mode %d is not a banded mode (constwo's switch reads the banded names only)", i, p->alnmode); }
-        else if (p->a.npfq > 0 || p->b.npfq > 0) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: annotated (spliced) groups are not on this path", i); }
-        else if (p->a.nils || p->b.nils) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: groups with discounted terminal gaps are not on this path", i); }
-        else if (p->a.len != p->b.len || p->a.left != 0 || p->b.left != 0 || p->a.right != p->a.len || p->b.right != p->b.len) { rc = G2G_ERR_ARG; snprintf(msg, sizeof msg, "pair %d: the two groups must have the same length and stand whole (%d and %d columns)", i, p->a.len, p->b.len); }
-        else if (p->alnmode == G2G_NTV_ALB && p->a.many + p->b.many > CR_NV_MEM) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: a naive-record division of %d members", i, p->a.many + p->b.many); }
-        if (rc == G2G_OK && (rc = check_problem(p)) != G2G_OK) snprintf(msg, sizeof msg, "pair %d: not a problem of this library (status %d)", i, rc);
-        if (rc != G2G_OK) { if (status) status[i] = rc; g2g_set_error("g2g_constwo_batch: %s", msg); return rc; }
+        size_t nm = 0;
+        const int rc = cr_check_pair(who, i, p, "constwo", &nm);
+        if (rc != G2G_OK) { if (status) status[i] = rc; return rc; }
         prob[(size_t) i] = p;
         vthr[(size_t) i] = sp.vab * thr;
-        const int kind = kind_of(p->alnmode);
-        const size_t nm = kind == 3 ? (size_t) p->a.many + p->b.many : kind == 1 ? (size_t) p->b.many : 0;
         nm_max = std::max(nm_max, nm);
-        cols += (size_t) p->a.len;
+        const size_t len = (size_t) p->a.len, cap = len / 2 + 2;
+        o_rng[(size_t) i] = out_bytes; out_bytes += (sizeof(int2) * cap + 15) & ~(size_t) 15;
+        o_col[(size_t) i] = out_bytes; if (colscore) out_bytes += (8 * len + 15) & ~(size_t) 15;
     }
-    const size_t lds = (nm_max * (8 * CR_W + 4) + 15) & ~(size_t) 15;
-    if (lds > 48 * 1024) { g2g_set_error("%s: a gap-free group of more than 1365 members on the _hf path", who); return G2G_ERR_MODE; }
+    if (!cr_lds_bytes(who, nm_max, &lds)) return G2G_ERR_MODE;
     if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
     if (!ctx->ok) return G2G_ERR_NODEVICE;
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return G2G_OK;
-    // the inputs as g2g_batch_prepare packs them (arrays a device builder left in HBM are read where they lie), and nothing else:
-    // no DP state, no trace
-    std::vector<DevProb> dp((size_t) n);
+    CrPairs dv(ctx, who, n);
+    int rc = dv.pack(prob.data(), sizeof(ConsregArgs), out_bytes);
+    if (rc != G2G_OK) return rc;
     std::vector<ConsregArgs> ar((size_t) n);
-    std::vector<DevPatch> patches;
-    std::vector<size_t> o_rng((size_t) n), o_col((size_t) n);
-    size_t in_bytes = 0, total = 0;
-    char *dev = 0;
-    size_t dev_cap = 0;
-    hipError_t e = hipSuccess;
-    std::vector<int> hn((size_t) n, 0);
-    size_t o_nr = 0, o_probs = 0, o_args = 0;
-    {
-        Blob bl(ctx);
-        bl.grow(staging_estimate(ctx, n, prob.data()) + sizeof(ConsregArgs) * (size_t) n);
-        o_probs = bl.put(0, 0);
-        bl.extend(o_probs + sizeof(DevProb) * (size_t) n);
-        o_args = bl.put(0, 0);
-        bl.extend(o_args + sizeof(ConsregArgs) * (size_t) n);
-        for (int i = 0; i < n; ++i) pack_problem(bl, prob[(size_t) i], dp[(size_t) i], patches);
-        bl.flush();
-        if (bl.oom) { g2g_set_error("%s: host staging buffer: out of (pinned) memory", who); return G2G_ERR_NOMEM; }
-        in_bytes = (bl.size() + 255) & ~(size_t) 255;
-        total = in_bytes;
-        o_nr = total; total += (4 * (size_t) n + 255) & ~(size_t) 255;
-        for (int i = 0; i < n; ++i) {
-            const size_t len = (size_t) prob[(size_t) i]->a.len, cap = len / 2 + 2;
-            o_rng[(size_t) i] = total; total += (sizeof(int2) * cap + 15) & ~(size_t) 15;
-            o_col[(size_t) i] = total; if (colscore) total += (8 * len + 15) & ~(size_t) 15;
-        }
-        dev = (char *) pool_take(ctx, total, &dev_cap);
-        if (!dev) { g2g_set_error("%s: out of device memory", who); (void) hipGetLastError(); return G2G_ERR_NOMEM; }
-        for (int i = 0; i < n; ++i) {
-            rebase_problem(dp[(size_t) i], dev);
-            ConsregArgs &a = ar[(size_t) i];
-            a.vthr = vthr[(size_t) i];
-            a.ranges = (int2 *) (dev + o_rng[(size_t) i]); a.cap = prob[(size_t) i]->a.len / 2 + 2;
-            a.nranges = (int *) (dev + o_nr) + i;
-            a.colscore = colscore ? (double *) (dev + o_col[(size_t) i]) : 0;
-        }
-        for (const DevPatch &pt : patches) *pt.field = pt.value;
-        memcpy(bl.data() + o_probs, dp.data(), sizeof(DevProb) * (size_t) n);
-        memcpy(bl.data() + o_args, ar.data(), sizeof(ConsregArgs) * (size_t) n);
-        e = hipMemcpyAsync(dev, bl.data(), bl.size(), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);        // (the staging buffer goes back to the context with bl)
+    for (int i = 0; i < n; ++i) {
+        ConsregArgs &a = ar[(size_t) i];
+        a.vthr = vthr[(size_t) i];
+        a.ranges = (int2 *) (dv.out() + o_rng[(size_t) i]); a.cap = prob[(size_t) i]->a.len / 2 + 2;
+        a.nranges = (int *) dv.out() + i;
+        a.colscore = colscore ? (double *) (dv.out() + o_col[(size_t) i]) : 0;
     }
-    const bool timed = g2g_opt(ctx, "CONSREG_TIMING") != 0;                // diagnostic switch: device events around the kernel (tools/consreg_probe.py)
-    if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[0], ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(g2g_consreg_kernel, dim3((unsigned) n), dim3(CR_T), lds, ctx->stream, (const DevProb *) (dev + o_probs), (const ConsregArgs *) (dev + o_args));
-        e = hipGetLastError();
+    dv.upload(ar.data(), "CONSREG_TIMING");
+    if (dv.e == hipSuccess) {
+        hipLaunchKernelGGL(g2g_consreg_kernel, dim3((unsigned) n), dim3(CR_T), lds, ctx->stream, dv.probs(), (const ConsregArgs *) dv.args());
+        dv.e = hipGetLastError();
     }
-    if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[1], ctx->stream);
-    // everything behind the inputs comes back in one copy
-    std::vector<char> back(total - in_bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    else (void) hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && timed) {                                        // read back as option CONSREG_KERNEL_MS (summed over the calls since it was cleared)
-        float ms = 0;
-        e = hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-        cr_note_ms(ctx, "CONSREG_KERNEL_MS", ms, true);
-    }
-    pool_give(ctx, dev, dev_cap);
-    if (e != hipSuccess) { g2g_set_error("g2g_constwo_batch: %s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
-    int rc = G2G_OK;
+    rc = dv.fetch("CONSREG_KERNEL_MS");
+    if (rc != G2G_OK) return rc;
+    const char *back = dv.back.data();
     for (int i = 0; i < n && rc == G2G_OK; ++i) {
         const int len = prob[(size_t) i]->a.len, cap = len / 2 + 2;
-        const int nr = ((const int *) (back.data() + (o_nr - in_bytes)))[i];
+        const int nr = ((const int *) back)[i];
         if (nr < 0 || nr > cap) { g2g_set_error("%s: a division produced more ranges than its slot holds", who); rc = G2G_ERR_DEVICE; break; }
         ranges[i] = (g2g_range *) malloc(sizeof(g2g_range) * (size_t) (nr ? nr : 1));
         if (!ranges[i]) { rc = G2G_ERR_NOMEM; break; }
-        memcpy(ranges[i], back.data() + (o_rng[(size_t) i] - in_bytes), sizeof(g2g_range) * (size_t) nr);
+        memcpy(ranges[i], back + o_rng[(size_t) i], sizeof(g2g_range) * (size_t) nr);
         nranges[i] = nr;
         if (colscore) {
             colscore[i] = (double *) malloc(8 * (size_t) len);
             if (!colscore[i]) { rc = G2G_ERR_NOMEM; break; }
-            memcpy(colscore[i], back.data() + (o_col[(size_t) i] - in_bytes), 8 * (size_t) len);
+            memcpy(colscore[i], back + o_col[(size_t) i], 8 * (size_t) len);
         }
     }
     if (rc != G2G_OK)
@@ -420,91 +443,45 @@ extern "C" int g2g_mayfuse_batch(g2g_ctx *ctx, int n, g2g_pwdm *const *pw, doubl
     for (int i = 0; i < n; ++i) { fuse[i] = 0; stop_col[i] = -1; if (status) status[i] = G2G_OK; }
     std::vector<const g2g_problem *> prob((size_t) n);
     std::vector<double> fthr((size_t) n);
-    size_t nm_max = 0;
+    size_t nm_max = 0, lds = 0;
     for (int i = 0; i < n; ++i) {
         const g2g_problem *p = pw[i] ? g2g_pwdm_problem(pw[i]) : 0;
         if (!p) { g2g_set_error("%s: a NULL pair", who); return G2G_ERR_ARG; }
-        int rc = G2G_OK;
-        char msg[160] = "";
-        if (p->alnmode < G2G_NGP_ALB || p->alnmode > G2G_NTV_ALB) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: mode %d is not a banded mode (mayfuse's switch reads the banded names only)", i, p->alnmode); }
-        else if (p->a.npfq > 0 || p->b.npfq > 0) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: annotated (spliced) groups are not on this path", i); }
-        else if (p->a.nils || p->b.nils) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: groups with discounted terminal gaps are not on this path", i); }
-        else if (p->a.len != p->b.len || p->a.left != 0 || p->b.left != 0 || p->a.right != p->a.len || p->b.right != p->b.len) { rc = G2G_ERR_ARG; snprintf(msg, sizeof msg, "pair %d: the two groups must have the same length and stand whole (%d and %d columns)", i, p->a.len, p->b.len); }
-        else if (p->alnmode == G2G_NTV_ALB && p->a.many + p->b.many > CR_NV_MEM) { rc = G2G_ERR_MODE; snprintf(msg, sizeof msg, "pair %d: a naive-record pair of %d members", i, p->a.many + p->b.many); }
-        if (rc == G2G_OK && (rc = check_problem(p)) != G2G_OK) snprintf(msg, sizeof msg, "pair %d: not a problem of this library (status %d)", i, rc);
-        if (rc != G2G_OK) { if (status) status[i] = rc; cr_err(who, "%s", msg); return rc; }
+        size_t nm = 0;
+        const int rc = cr_check_pair(who, i, p, "mayfuse", &nm);
+        if (rc != G2G_OK) { if (status) status[i] = rc; return rc; }
         prob[(size_t) i] = p;
         // fthr = (VTYPE) -((2 * localprm.u + localprm.v)) * a->sumwt * b->sumwt (consreg.cc:73): u and v are floats there, the cast
         // binds to the negated sum, the products run left to right in VTYPE = double
         const float uf = (float) u, vf = (float) v;
         fthr[(size_t) i] = (double) -((2 * uf + vf)) * p->a.sumwt * p->b.sumwt;
-        const int kind = kind_of(p->alnmode);
-        const size_t nm = kind == 3 ? (size_t) p->a.many + p->b.many : kind == 1 ? (size_t) p->b.many : 0;
         nm_max = std::max(nm_max, nm);
     }
-    const size_t lds = (nm_max * (8 * CR_W + 4) + 15) & ~(size_t) 15;
-    if (lds > 48 * 1024) { g2g_set_error("%s: a gap-free group of more than 1365 members on the _hf path", who); return G2G_ERR_MODE; }
+    if (!cr_lds_bytes(who, nm_max, &lds)) return G2G_ERR_MODE;
     if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
     if (!ctx->ok) return G2G_ERR_NODEVICE;
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return G2G_OK;
-    std::vector<DevProb> dp((size_t) n);
+    CrPairs dv(ctx, who, n);
+    int rc = dv.pack(prob.data(), sizeof(MayfuseArgs), (sizeof(int2) * (size_t) n + 255) & ~(size_t) 255);   // behind the inputs: {fuse, stop_col}[n]
+    if (rc != G2G_OK) return rc;
     std::vector<MayfuseArgs> ar((size_t) n);
-    std::vector<DevPatch> patches;
-    size_t in_bytes = 0, total = 0, o_probs = 0, o_args = 0;
-    char *dev = 0;
-    size_t dev_cap = 0;
-    hipError_t e = hipSuccess;
-    {
-        Blob bl(ctx);
-        bl.grow(staging_estimate(ctx, n, prob.data()) + sizeof(MayfuseArgs) * (size_t) n);
-        o_probs = bl.put(0, 0);
-        bl.extend(o_probs + sizeof(DevProb) * (size_t) n);
-        o_args = bl.put(0, 0);
-        bl.extend(o_args + sizeof(MayfuseArgs) * (size_t) n);
-        for (int i = 0; i < n; ++i) pack_problem(bl, prob[(size_t) i], dp[(size_t) i], patches);
-        bl.flush();
-        if (bl.oom) { g2g_set_error("%s: host staging buffer: out of (pinned) memory", who); return G2G_ERR_NOMEM; }
-        in_bytes = (bl.size() + 255) & ~(size_t) 255;
-        total = in_bytes + ((sizeof(int2) * (size_t) n + 255) & ~(size_t) 255);
-        dev = (char *) pool_take(ctx, total, &dev_cap);
-        if (!dev) { g2g_set_error("%s: out of device memory", who); (void) hipGetLastError(); return G2G_ERR_NOMEM; }
-        for (int i = 0; i < n; ++i) {
-            rebase_problem(dp[(size_t) i], dev);
-            ar[(size_t) i].fthr = fthr[(size_t) i];
-            ar[(size_t) i].out = (int2 *) (dev + in_bytes) + i;
-        }
-        for (const DevPatch &pt : patches) *pt.field = pt.value;
-        memcpy(bl.data() + o_probs, dp.data(), sizeof(DevProb) * (size_t) n);
-        memcpy(bl.data() + o_args, ar.data(), sizeof(MayfuseArgs) * (size_t) n);
-        e = hipMemcpyAsync(dev, bl.data(), bl.size(), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    for (int i = 0; i < n; ++i) { ar[(size_t) i].fthr = fthr[(size_t) i]; ar[(size_t) i].out = (int2 *) dv.out() + i; }
+    dv.upload(ar.data(), "FUSE_TIMING");
+    if (dv.e == hipSuccess) {
+        hipLaunchKernelGGL(g2g_mayfuse_kernel, dim3((unsigned) n), dim3(CR_T), lds, ctx->stream, dv.probs(), (const MayfuseArgs *) dv.args());
+        dv.e = hipGetLastError();
     }
-    const bool timed = g2g_opt(ctx, "FUSE_TIMING") != 0;                   // diagnostic switch: device events around the kernel (tools/fuse_probe.py)
-    if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[0], ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(g2g_mayfuse_kernel, dim3((unsigned) n), dim3(CR_T), lds, ctx->stream, (const DevProb *) (dev + o_probs), (const MayfuseArgs *) (dev + o_args));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && timed) e = hipEventRecord(ctx->ev[1], ctx->stream);
-    std::vector<int2> back((size_t) n);
-    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), dev + in_bytes, sizeof(int2) * (size_t) n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    else (void) hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && timed) {                                        // read back as option FUSE_KERNEL_MS (summed over the calls since it was cleared)
-        float ms = 0;
-        e = hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-        cr_note_ms(ctx, "FUSE_KERNEL_MS", ms, true);
-    }
-    pool_give(ctx, dev, dev_cap);
-    if (e != hipSuccess) { cr_err(who, "%s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
+    rc = dv.fetch("FUSE_KERNEL_MS");
+    if (rc != G2G_OK) return rc;
+    const int2 *back = (const int2 *) dv.back.data();
     for (int i = 0; i < n; ++i) {
         const int len = prob[(size_t) i]->a.len;
-        if ((back[(size_t) i].x != 0 && back[(size_t) i].x != 1) || back[(size_t) i].y < -1 || back[(size_t) i].y >= len || (back[(size_t) i].x == 1) != (back[(size_t) i].y < 0)) {
-            cr_err(who, "pair %d came back as (%d, %d)", i, back[(size_t) i].x, back[(size_t) i].y);
+        if ((back[i].x != 0 && back[i].x != 1) || back[i].y < -1 || back[i].y >= len || (back[i].x == 1) != (back[i].y < 0)) {
+            g2g_errorf(who, "pair %d came back as (%d, %d)", i, back[i].x, back[i].y);
             return G2G_ERR_DEVICE;
         }
-        fuse[i] = back[(size_t) i].x; stop_col[i] = back[(size_t) i].y;
+        fuse[i] = back[i].x; stop_col[i] = back[i].y;
     }
     return G2G_OK;
 }
@@ -790,7 +767,7 @@ int cr_mode_check(const g2g_params *prm, const char *who)
 }
 void cr_fuse_note(g2g_ctx *ctx, const CrBuildTimes &tm)
 {
-    cr_note_ms(ctx, "FUSE_BUILD_MS", tm.build, false); cr_note_ms(ctx, "FUSE_HOST_MS", tm.host, false);
+    g2g_note_ms(ctx, "FUSE_BUILD_MS", tm.build, false); g2g_note_ms(ctx, "FUSE_HOST_MS", tm.host, false);
 }
 int cr_consreg_run(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, int len, const uint8_t *codes, const double *weight,
                    const g2g_tree *tree, const g2g_subset *groups, int dissim, g2g_range **out, int *nout, const char *who);
@@ -819,11 +796,11 @@ extern "C" int g2g_consregss(g2g_ctx *ctx, const g2g_params *prm, int many, int 
     if (!prm || !codes || !tree || !out || len < 1) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
     memset(out, 0, sizeof *out);
     if (many < 2) { g2g_set_error("%s: fewer than two members", who); return G2G_ERR_ARG; }
-    if (left < 0 || right > len || left >= right) { cr_err(who, "the range [%d, %d) is empty or leaves the %d columns", left, right, len); return G2G_ERR_ARG; }
+    if (left < 0 || right > len || left >= right) { g2g_errorf(who, "the range [%d, %d) is empty or leaves the %d columns", left, right, len); return G2G_ERR_ARG; }
     int rc = cr_mode_check(prm, who);
     if (rc != G2G_OK) return rc;
     const int nl = groups ? groups->num : many;
-    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { cr_err(who, "%s", bad); return G2G_ERR_ARG; }
+    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { g2g_errorf(who, "%s", bad); return G2G_ERR_ARG; }
     if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
     if (!ctx->ok) return G2G_ERR_NODEVICE;
     const bool timed = g2g_opt(ctx, "FUSE_TIMING") != 0;
@@ -853,7 +830,7 @@ extern "C" int g2g_consreg_groups(g2g_ctx *ctx, const g2g_params *prm, double th
     const int nl = groups ? groups->num : many;
     if (many < 2 || nl < 2) { g2g_set_error("%s: fewer than two groups have no division into two sons", who); return G2G_ERR_ARG; }
     if (!(thr > 0)) { g2g_set_error("%s: thr must be positive", who); return G2G_ERR_ARG; }
-    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { cr_err(who, "%s", bad); return G2G_ERR_ARG; }
+    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { g2g_errorf(who, "%s", bad); return G2G_ERR_ARG; }
     return cr_consreg_run(ctx, prm, thr, many, len, codes, weight, tree, groups, dissim, out, nout, who);
 }
 
@@ -878,7 +855,7 @@ static int cr_refine_plan(const char *who, g2g_ctx *ctx, const g2g_params *prm, 
     int rc = cr_mode_check(prm, who);
     if (rc != G2G_OK) return rc;
     const int nl = groups ? groups->num : many;
-    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { cr_err(who, "%s", bad); return G2G_ERR_ARG; }
+    if (const char *bad = cr_check_relation(tree, nl, groups, many, 0)) { g2g_errorf(who, "%s", bad); return G2G_ERR_ARG; }
     if (!ctx) { g2g_set_error("%s: no context", who); return G2G_ERR_ARG; }
     if (!ctx->ok) return G2G_ERR_NODEVICE;
     const bool timed = g2g_opt(ctx, "FUSE_TIMING") != 0;
@@ -1091,7 +1068,7 @@ int cr_consreg_run(g2g_ctx *ctx, const g2g_params *prm, double thr, int many, in
     *out = cr_hand_out(united);
     *nout = (int) united.size();
     t_host += cr_now() - t3;
-    if (timed) { cr_note_ms(ctx, "CONSREG_BUILD_MS", t_build, false); cr_note_ms(ctx, "CONSREG_CONSTWO_MS", t_two, false); cr_note_ms(ctx, "CONSREG_HOST_MS", t_host, false); }
+    if (timed) { g2g_note_ms(ctx, "CONSREG_BUILD_MS", t_build, false); g2g_note_ms(ctx, "CONSREG_CONSTWO_MS", t_two, false); g2g_note_ms(ctx, "CONSREG_HOST_MS", t_host, false); }
     return *out ? G2G_OK : G2G_ERR_NOMEM;
 }
 }

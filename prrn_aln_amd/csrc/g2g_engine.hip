@@ -43,6 +43,16 @@ void g2g_set_error(const char *fmt, const char *a)
     snprintf(buf, sizeof buf, fmt, a);
     g_err = buf;
 }
+void g2g_errorf(const char *who, const char *fmt, ...)
+{
+    char buf[512];
+    const int at = snprintf(buf, sizeof buf, "%s: ", who);
+    va_list ap;
+    va_start(ap, fmt);
+    if (at >= 0 && (size_t) at < sizeof buf) vsnprintf(buf + at, sizeof buf - (size_t) at, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+}
 extern "C" const char *g2g_last_error(void) { return g_err.c_str(); }
 extern "C" int g2g_abi_version(void) { return G2G_ABI_VERSION; }
 
@@ -93,6 +103,22 @@ static const char *g2g_opt(const g2g_ctx *c, const char *name)
     char env[96];
     snprintf(env, sizeof env, "G2G_%s", name);
     return getenv(env);
+}
+// A stage's timing switch leaves what it measured as an option of the context ("%.6f" milliseconds); add: summed onto the
+// value the option holds.  g2g_note_events: the time between two recorded events of a stream that has been waited for.
+static void g2g_note_ms(g2g_ctx *c, const char *name, double ms, bool add)
+{
+    if (add) { const char *old = g2g_opt(c, name); if (old) ms += atof(old); }
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.6f", ms);
+    c->opt[name] = std::make_pair(true, std::string(buf));
+}
+static hipError_t g2g_note_events(g2g_ctx *c, const char *name, hipEvent_t from, hipEvent_t to, bool add)
+{
+    float ms = 0;
+    const hipError_t e = hipEventElapsedTime(&ms, from, to);
+    g2g_note_ms(c, name, ms, add);
+    return e;
 }
 extern "C" int g2g_set_option(g2g_ctx *c, const char *name, const char *value)
 {

@@ -4,5 +4,7 @@
 #include "../../include/g2g.h"
 
 void g2g_set_error(const char *fmt, const char *arg);
+// "<who>: <formatted text>" -- for a message with more than one argument
+void g2g_errorf(const char *who, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #endif

@@ -321,12 +321,6 @@ double km_pamcorrect(double x)                                        // divseq.
     if (x <= 0) return (0);
     return (100. * x);
 }
-void km_error(const char *who, const char *msg)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", who, msg);
-    g2g_set_error("%s", buf);
-}
 // what both entries come down to.  width / seed: the seed (bit o: a '1' at offset o; the continuous seed of k is its k low bits);
 // p0, p1: the row of qdiv's param; classes: only where spec (the spec entry's profile kernel)
 struct KmPlan { int molc, k, measure, width; unsigned nalpha, seed; double p0, p1; bool spec; uint8_t classes[256]; };
@@ -433,9 +427,7 @@ int km_from_counts(const char *who, const KmPlan &pl, int npairs, const int32_t 
     for (int p = 0; p < npairs; ++p) {
         const int32_t *c = counts + 3 * (size_t) p;
         if (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] > (c[1] < c[2] ? c[1] : c[2])) {
-            char msg[96];
-            snprintf(msg, sizeof msg, "pair %d: counts %d %d %d are no s <= min(Ta, Tb)", p, c[0], c[1], c[2]);
-            km_error(who, msg);
+            g2g_errorf(who, "pair %d: counts %d %d %d are no s <= min(Ta, Tb)", p, c[0], c[1], c[2]);
             return G2G_ERR_ARG;
         }
         dist[p] = 100. * km_qdiv(c[0], c[1], c[2], pl.measure, pl.p0, pl.p1);   // kcmp_main, qdiv.cc:239
@@ -490,9 +482,7 @@ int km_batch(const char *who, g2g_ctx *ctx, const KmPlan &pl, int nseq, const g2
     if (!all)
         for (int p = 0; p < npairs; ++p)
             if (ia[p] < 0 || ia[p] >= nseq || ib[p] < 0 || ib[p] >= nseq) {
-                char msg[96];
-                snprintf(msg, sizeof msg, "pair %d: index %d or %d outside 0 .. %d", p, ia[p], ib[p], nseq - 1);
-                km_error(who, msg);
+                g2g_errorf(who, "pair %d: index %d or %d outside 0 .. %d", p, ia[p], ib[p], nseq - 1);
                 return G2G_ERR_ARG;
             }
     // the pool holds each sequence's window, left .. right - 1; the word positions give the list strides
@@ -501,16 +491,13 @@ int km_batch(const char *who, g2g_ctx *ctx, const KmPlan &pl, int nseq, const g2
     int wmax = 0;
     for (int i = 0; i < nseq; ++i) {
         const g2g_dseq &s = seqs[i];
-        char msg[128];
         if ((!s.res && s.right > s.left) || s.left < 0 || s.right < s.left || s.right > s.len) {
-            snprintf(msg, sizeof msg, "sequence %d: no residues, or not 0 <= left <= right <= len", i);
-            km_error(who, msg);
+            g2g_errorf(who, "sequence %d: no residues, or not 0 <= left <= right <= len", i);
             return G2G_ERR_ARG;
         }
         const long long w = std::max(0LL, (long long) (s.right - s.left) - 2 * pl.width + 1);
         if (w > G2G_KMER_MAX_WINDOW) {
-            snprintf(msg, sizeof msg, "sequence %d has %lld word positions, more than %d", i, w, G2G_KMER_MAX_WINDOW);
-            km_error(who, msg);
+            g2g_errorf(who, "sequence %d has %lld word positions, more than %d", i, w, G2G_KMER_MAX_WINDOW);
             return G2G_ERR_ARG;
         }
         hs[i].res = (long long) pool; hs[i].list = (long long) lists; hs[i].words = (int) w; hs[i].pad = 0;
@@ -581,16 +568,10 @@ int km_batch(const char *who, g2g_ctx *ctx, const KmPlan &pl, int nseq, const g2
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess && timed) {                                   // read back as options KMER_PROFILE_MS / KMER_PAIRS_MS (g2g_get_option)
         const char *name[2] = {"KMER_PROFILE_MS", "KMER_PAIRS_MS"};
-        for (int h = 0; h < 2 && e == hipSuccess; ++h) {
-            float ms = 0;
-            e = hipEventElapsedTime(&ms, ctx->ev[2 * h], ctx->ev[2 * h + 1]);
-            char buf[32];
-            snprintf(buf, sizeof buf, "%.6f", ms);
-            ctx->opt[name[h]] = std::make_pair(true, std::string(buf));
-        }
+        for (int h = 0; h < 2 && e == hipSuccess; ++h) e = g2g_note_events(ctx, name[h], ctx->ev[2 * h], ctx->ev[2 * h + 1], false);
     }
     (void) hipFree(dev);
-    if (e != hipSuccess) { km_error(who, hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
+    if (e != hipSuccess) { g2g_errorf(who, "%s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
     return km_from_counts(who, pl, npairs, counts, dist);
 }
 }

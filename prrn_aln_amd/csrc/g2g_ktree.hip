@@ -113,13 +113,7 @@ extern "C" int g2g_msa_divergence(g2g_ctx *ctx, int many, int len, const uint8_t
     if (e == hipSuccess) e = hipMemcpyAsync(dist, dev + o_dist, 8 * np, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && counts) e = hipMemcpyAsync(counts, dev + o_cnt, 16 * np, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && timed) {                                  // read back as option KTREE_KERNEL_MS (g2g_get_option)
-        float ms = 0;
-        e = hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-        char buf[32];
-        snprintf(buf, sizeof buf, "%.6f", ms);
-        ctx->opt["KTREE_KERNEL_MS"] = std::make_pair(true, std::string(buf));
-    }
+    if (e == hipSuccess && timed) e = g2g_note_events(ctx, "KTREE_KERNEL_MS", ctx->ev[0], ctx->ev[1], false);   // (g2g_get_option reads it)
     (void) hipFree(dev);
     if (e != hipSuccess) { g2g_set_error("g2g_msa_divergence: %s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
     return G2G_OK;
@@ -294,9 +288,7 @@ static int kt_tree_from_dist(const char *who, int many, const double *dist, cons
         for (int i = 0; i < j; ++i) {
             const double d = dist[kt_elem(i, j)];
             if (!(d >= 0)) {                                          // (NaN included: a pair of members without a common column)
-                char msg[128];
-                snprintf(msg, sizeof msg, "%s: distance of members %d and %d is %s", who, i, j, d != d ? "not a number" : "negative");
-                g2g_set_error("%s", msg);
+                g2g_errorf(who, "distance of members %d and %d is %s", i, j, d != d ? "not a number" : "negative");
                 return G2G_ERR_ARG;
             }
         }

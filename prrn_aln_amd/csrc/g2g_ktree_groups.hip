@@ -123,19 +123,18 @@ extern "C" __global__ void __launch_bounds__(64) g2g_grp_reduce_kernel(const int
 // groups partition 0 .. many - 1, every group has a member, and no pair's counters can pass INT_MAX
 static int kg_check_groups(const char *who, int many, int len, const g2g_subset *ss)
 {
-    char msg[192];
     if (!ss || !ss->start || !ss->member || ss->num < 2 || ss->num > many || ss->elms != many || ss->start[0] != 0 || ss->start[ss->num] != many) {
-        snprintf(msg, sizeof msg, "%s: the groups must be at least two and partition the %d members", who, many);
-        g2g_set_error("%s", msg); return G2G_ERR_ARG;
+        g2g_errorf(who, "the groups must be at least two and partition the %d members", many);
+        return G2G_ERR_ARG;
     }
     std::vector<char> seen((size_t) many, 0);
     int big[2] = {-1, -1};                                            // the two largest groups: the pair whose counters go highest
     for (int g = 0; g < ss->num; ++g) {
         const int s = ss->start[g], e = ss->start[g + 1];
-        if (s >= e || e > many) { snprintf(msg, sizeof msg, "%s: group %d is empty or its bounds do not ascend", who, g); g2g_set_error("%s", msg); return G2G_ERR_ARG; }
+        if (s >= e || e > many) { g2g_errorf(who, "group %d is empty or its bounds do not ascend", g); return G2G_ERR_ARG; }
         for (int k = s; k < e; ++k) {
             const int m = ss->member[k];
-            if (m < 0 || m >= many || seen[m]) { snprintf(msg, sizeof msg, "%s: group %d: member %d is out of range or listed twice", who, g, m); g2g_set_error("%s", msg); return G2G_ERR_ARG; }
+            if (m < 0 || m >= many || seen[m]) { g2g_errorf(who, "group %d: member %d is out of range or listed twice", g, m); return G2G_ERR_ARG; }
             seen[m] = 1;
         }
         auto size = [&](int h) { return h < 0 ? 0 : ss->start[h + 1] - ss->start[h]; };
@@ -144,9 +143,8 @@ static int kg_check_groups(const char *who, int many, int len, const g2g_subset 
     }
     const long long top = (long long) len * (ss->start[big[0] + 1] - ss->start[big[0]]) * (ss->start[big[1] + 1] - ss->start[big[1]]);
     if (top >= (1LL << 31)) {
-        snprintf(msg, sizeof msg, "%s: groups %d and %d: len x ni x nj = %lld does not fit the reference's int counters", who,
-                 std::min(big[0], big[1]), std::max(big[0], big[1]), top);
-        g2g_set_error("%s", msg); return G2G_ERR_ARG;
+        g2g_errorf(who, "groups %d and %d: len x ni x nj = %lld does not fit the reference's int counters", std::min(big[0], big[1]), std::max(big[0], big[1]), top);
+        return G2G_ERR_ARG;
     }
     return G2G_OK;
 }
@@ -208,27 +206,16 @@ static int kg_divergence(const char *who, g2g_ctx *ctx, int many, int len, const
     if (e == hipSuccess && counts) e = hipMemcpyAsync(counts, dev + o_cnt, 16 * npg, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && slot_dist) e = hipMemcpyAsync(slot_dist, dev + o_pdist, 8 * npm, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && timed) {                                  // read back as option KTREE_GROUPS_KERNEL_MS (g2g_get_option)
-        float ms = 0;
-        e = hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
-        char buf[32];
-        snprintf(buf, sizeof buf, "%.6f", ms);
-        ctx->opt["KTREE_GROUPS_KERNEL_MS"] = std::make_pair(true, std::string(buf));
-    }
+    if (e == hipSuccess && timed) e = g2g_note_events(ctx, "KTREE_GROUPS_KERNEL_MS", ctx->ev[0], ctx->ev[1], false);   // (g2g_get_option reads it)
     (void) hipFree(dev);
-    if (e != hipSuccess) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: %s", who, hipGetErrorString(e));
-        g2g_set_error("%s", msg); (void) hipGetLastError(); return G2G_ERR_DEVICE;
-    }
+    if (e != hipSuccess) { g2g_errorf(who, "%s", hipGetErrorString(e)); (void) hipGetLastError(); return G2G_ERR_DEVICE; }
     return G2G_OK;
 }
 
 static int kg_check_args(const char *who, int many, int len, const uint8_t *codes, const g2g_subset *groups)
 {
-    char msg[128];
-    if (!codes || !groups) { snprintf(msg, sizeof msg, "%s: bad argument", who); g2g_set_error("%s", msg); return G2G_ERR_ARG; }
-    if (many < 2 || many > G2G_KTREE_MAX_MEMBERS || len < 1) { snprintf(msg, sizeof msg, "%s: 2 <= many <= 4096 and len >= 1", who); g2g_set_error("%s", msg); return G2G_ERR_ARG; }
+    if (!codes || !groups) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
+    if (many < 2 || many > G2G_KTREE_MAX_MEMBERS || len < 1) { g2g_set_error("%s: 2 <= many <= 4096 and len >= 1", who); return G2G_ERR_ARG; }
     return kg_check_groups(who, many, len, groups);
 }
 

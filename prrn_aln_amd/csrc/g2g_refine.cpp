@@ -20,7 +20,6 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <stdarg.h>
 #include <string.h>
 #include <cmath>
 #include <string>
@@ -37,17 +36,6 @@
 extern "C" void g2g_ctx_counters(const g2g_ctx *c, long long out[4]);
 
 namespace {
-
-void rf_err(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-void rf_err(const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g2g_set_error("%s", buf);
-}
 
 const uint8_t GAP = 1;
 const double FEPS = 1.0e-7;                                   // reference src/cmn.h:54
@@ -497,7 +485,7 @@ int refine_loop(g2g_ctx *ctx, const g2g_params *prm, g2g_refine_opts O, const Re
                     if (st_r == G2G_OK) continue;
                     rc_all = st_r < 0 ? st_r : G2G_ERR_DEVICE;
                     if (r == O.rank && !local_err.empty()) g2g_set_error("%s", local_err.c_str());
-                    else { rf_err("%s: rank %d failed (its code is this call's return value)", who, r); }
+                    else { g2g_errorf(who, "rank %d failed (its code is this call's return value)", r); }
                 }
             }
             int seen = 0;
@@ -685,15 +673,15 @@ int refine_planned_run(const char *who, g2g_ctx *ctx, const g2g_params *prm, int
     if (plan->status != G2G_PLAN_OK && !nothing) { g2g_set_error("%s: a plan's status is 0 or G2G_PLAN_NOTHING_TO_REFINE", who); return G2G_ERR_ARG; }
     if (nr < 0 || (nr > 0 && (!plan->ranges || !plan->range_rel))) { g2g_set_error("%s: the plan's ranges are missing", who); return G2G_ERR_ARG; }
     if (nr > 0) {
-        if (const char *why = check_relation(&plan->whole, many, tree_nodes)) { rf_err("%s: malformed plan (the whole-MSA relation): %s", who, why); return G2G_ERR_ARG; }
+        if (const char *why = check_relation(&plan->whole, many, tree_nodes)) { g2g_errorf(who, "malformed plan (the whole-MSA relation): %s", why); return G2G_ERR_ARG; }
     }
     for (int r = 0; r < nr; ++r) {
         const g2g_range &g = plan->ranges[r];
         if (g.left < 0 || g.right > len || g.left >= g.right || (r > 0 && g.left < plan->ranges[r - 1].right)) {
-            rf_err("%s: malformed plan: range %d [%d, %d) is empty, leaves the %d columns or does not lie behind range %d", who, r, g.left, g.right, len, r - 1);
+            g2g_errorf(who, "malformed plan: range %d [%d, %d) is empty, leaves the %d columns or does not lie behind range %d", r, g.left, g.right, len, r - 1);
             return G2G_ERR_ARG;
         }
-        if (const char *why = check_relation(&plan->range_rel[r], many, plan->whole.n_nodes)) { rf_err("%s: malformed plan (the relation of range %d): %s", who, r, why); return G2G_ERR_ARG; }
+        if (const char *why = check_relation(&plan->range_rel[r], many, plan->whole.n_nodes)) { g2g_errorf(who, "malformed plan (the relation of range %d): %s", r, why); return G2G_ERR_ARG; }
     }
     // a leaf group without a residue inside its range: what the reference does with the empty mSeq is not restated
     for (int r = 0; r < nr; ++r) {
@@ -704,7 +692,7 @@ int refine_planned_run(const char *who, g2g_ctx *ctx, const g2g_params *prm, int
             for (int c = plan->ranges[r].left; c < plan->ranges[r].right && !any; ++c)
                 for (int i = rel.ss.start[g]; i < rel.ss.start[g + 1] && !any; ++i) any = codes[(size_t) c * many + rel.ss.member[i]] != GAP;
             if (!any) {
-                rf_err("%s: group %d of range %d [%d, %d) has no residue inside the range", who, g, r, plan->ranges[r].left, plan->ranges[r].right);
+                g2g_errorf(who, "group %d of range %d [%d, %d) has no residue inside the range", g, r, plan->ranges[r].left, plan->ranges[r].right);
                 return G2G_ERR_MODE;
             }
         }
@@ -798,7 +786,7 @@ extern "C" int g2g_refine_planned(g2g_ctx *ctx, const g2g_params *prm, double th
         g2g_set_error("%s: the tree must have 2 * many - 1 nodes (leaves 0 .. many - 1 = the members)", who);
         return G2G_ERR_ARG;
     }
-    if (const char *why = check_tree(tree, many)) { rf_err("%s: malformed tree: %s", who, why); return G2G_ERR_ARG; }
+    if (const char *why = check_tree(tree, many)) { g2g_errorf(who, "malformed tree: %s", why); return G2G_ERR_ARG; }
     g2g_refine_opts O;
     if (int rc = fill_opts(opts, O, who)) return rc;
 
@@ -823,13 +811,13 @@ extern "C" int g2g_refine_planned_groups(g2g_ctx *ctx, const g2g_params *prm, do
     const char *who = "g2g_refine_planned_groups";
     if (int rc = refine_planned_args(who, ctx, prm, many, len, codes, tree, plan, opts, out_codes, out_len, rstat, nrstat)) return rc;
     if (!groups) { g2g_set_error("%s: bad argument", who); return G2G_ERR_ARG; }
-    if (const char *why = check_subset(groups, many)) { rf_err("%s: malformed groups: %s", who, why); return G2G_ERR_ARG; }
+    if (const char *why = check_subset(groups, many)) { g2g_errorf(who, "malformed groups: %s", why); return G2G_ERR_ARG; }
     if (groups->num < 2) { g2g_set_error("%s: fewer than two groups", who); return G2G_ERR_ARG; }
     if (tree->n_nodes != 2 * groups->num - 1 || !tree->left || !tree->right || !tree->parent || !tree->vol || !tree->cur) {
         g2g_set_error("%s: the tree must have 2 * num - 1 nodes (leaves 0 .. num - 1 = the groups)", who);
         return G2G_ERR_ARG;
     }
-    if (const char *why = check_tree(tree, groups->num)) { rf_err("%s: malformed tree: %s", who, why); return G2G_ERR_ARG; }
+    if (const char *why = check_tree(tree, groups->num)) { g2g_errorf(who, "malformed tree: %s", why); return G2G_ERR_ARG; }
     g2g_refine_opts O;
     if (int rc = fill_opts(opts, O, who)) return rc;
 
@@ -850,7 +838,7 @@ extern "C" int g2g_refine_planned_groups(g2g_ctx *ctx, const g2g_params *prm, do
         for (int g = 0; g < groups->num; ++g)
             for (int i = groups->start[g] + 1; i < groups->start[g + 1]; ++i)
                 if (of[(size_t) groups->member[i]] != of[(size_t) groups->member[groups->start[g]]]) {
-                    rf_err("%s: the relation of range %d of the plan divides group %d", who, r, g);
+                    g2g_errorf(who, "the relation of range %d of the plan divides group %d", r, g);
                     return G2G_ERR_ARG;
                 }
     }
@@ -933,7 +921,7 @@ extern "C" int g2g_progressive(g2g_ctx *ctx, const g2g_params *prm, int nseq, co
     if ((float) prm->tgapf != 1.f) { g2g_set_error("%s: the terminal-gap discount is not on this path", who); return G2G_ERR_MODE; }
     for (int i = 0; i < nseq; ++i)
         if (!seqs[i].res || seqs[i].len < 1 || seqs[i].left != 0 || seqs[i].right != seqs[i].len) {
-            rf_err("%s: sequence %d must be given whole (left = 0, right = len >= 1)", who, i);
+            g2g_errorf(who, "sequence %d must be given whole (left = 0, right = len >= 1)", i);
             return G2G_ERR_ARG;
         }
     if (tree->n_nodes != 2 * nseq - 1 || !tree->left || !tree->right || !tree->parent) {
@@ -941,7 +929,7 @@ extern "C" int g2g_progressive(g2g_ctx *ctx, const g2g_params *prm, int nseq, co
         return G2G_ERR_ARG;
     }
     int bad = -1;
-    if (const char *why = check_guide_tree(tree, nseq, &bad)) { rf_err("%s: malformed tree at node %d: %s", who, bad, why); return G2G_ERR_ARG; }
+    if (const char *why = check_guide_tree(tree, nseq, &bad)) { g2g_errorf(who, "malformed tree at node %d: %s", bad, why); return G2G_ERR_ARG; }
 
     const int nn = tree->n_nodes;
     std::vector<ProgNode> N((size_t) nn);
@@ -987,13 +975,13 @@ extern "C" int g2g_progressive(g2g_ctx *ctx, const g2g_params *prm, int nseq, co
         if (rc == G2G_OK) {
             if (O.aligner) {
                 rc = O.aligner(O.aligner_user, nw, pw.data(), scr.data(), skl.data(), nskl.data(), st.data());
-                if (rc != G2G_OK) rf_err("%s: the aligner callback failed in wave %d", who, S.waves);
+                if (rc != G2G_OK) g2g_errorf(who, "the aligner callback failed in wave %d", S.waves);
             } else rc = g2g_align2_batch(ctx, nw, pw.data(), scr.data(), skl.data(), nskl.data(), st.data());
             ++S.waves;
             if (nw > S.largest_wave) S.largest_wave = nw;
         }
         for (int i = 0; i < nw && rc == G2G_OK; ++i)
-            if (st[i] != 0) { rc = st[i]; rf_err("%s: the DP of node %d came back with status %d", who, wave[i], st[i]); }
+            if (st[i] != 0) { rc = st[i]; g2g_errorf(who, "the DP of node %d came back with status %d", wave[i], st[i]); }
         const double t_wave = now() - t_begin;
         for (int i = 0; i < nw && rc == G2G_OK; ++i) {
             const int k = wave[i];
@@ -1008,7 +996,7 @@ extern "C" int g2g_progressive(g2g_ctx *ctx, const g2g_params *prm, int nseq, co
             d.ra = A.blk.len; d.rb = B.blk.len;
             ProgNode &v = N[(size_t) k];
             if (!skl[i] || !join_columns(d, Skl(skl[i], skl[i] + nskl[i]), na + nb, v.blk)) {
-                rf_err("%s: the skeleton of node %d does not describe an alignment of its two sons", who, k);
+                g2g_errorf(who, "the skeleton of node %d does not describe an alignment of its two sons", k);
                 rc = G2G_ERR_DEVICE;
                 break;
             }
